@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Benchmark of the SMSUT hot path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W [--workload ugan|unet] [--per-gpu-batch B]
+    python bench.py --gpus N --steps K --warmup W [--workload ugan|unet] [--per-gpu-batch B] [--dump-outputs DIR] [--full]
 
 Metric (BASELINE.json): slices/sec of the uganConsisTrainer step @256x256.  A "step" is one full iteration of
 reference trainer/uganConsisTrainer.py:110-203 (D-step with WGAN-GP double backward + G-step with cycle pass,
@@ -10,7 +10,10 @@ resident in HBM.  Per GPU: B/2 labeled + B/2 unlabeled slices (default B=16 = re
 config 3); N>1 is pure data parallel, one process per GPU, flat RCCL all-reduce of D and G gradients (weak scaling).
 ``--workload unet`` times BASELINE config 2 instead (U-Net fwd + DiceCE + bwd + SGD, 32x1x256x256, 5 classes).
 
-Rank 0 prints ONE JSON line.  ``roofline`` is measured live with HIP events on the launch stream around the
+Rank 0 prints ONE JSON line.  A plain run sets up, warms up, times the K steps, writes the last step's outputs when
+``--dump-outputs DIR`` is given (``dump_outputs``) and prints the line; every other leg below runs only with ``--full``
+(each still switched off by its ``--no-*`` option).  ``end_to_end`` repeats the iteration with the host reading its scalars
+back.  ``roofline`` is measured live with HIP events on the launch stream around the
 dominant kernel -- the device kernel with the largest total time in the committed rocprofv3 summary of the iteration
 (profiles/r05_ugan_kernel_stats.csv: the register-row 3x3 weight gradient, input-side-IN form), launched through the
 entry point and with the arguments ops.py uses; ``roofline_fwd`` is the Winograd forward conv of r03's line, in the form
@@ -89,6 +92,36 @@ def pmc_fwd(key):
             return json.load(f).get(key, {})
     except (OSError, ValueError):
         return {}
+
+
+DUMP_BYTES_MAX = 60 * 10 ** 6            # under 64 MB with the .npy headers
+DUMP_SAMPLE_SEED = 20240
+DUMP_WHOLE = 4096                        # arrays up to this many elements are never sampled
+
+
+def dump_outputs(out_dir, scalars, nets):
+    """Write what the last timed step handed its caller as ``out_dir/<name>.npy``: ``loss_scalars`` (the tensor the step returned)
+    and ``<net>.<state_dict key>`` for every network the step trained (its parameters after that step's optimizer update).
+    Floating arrays are written as float32 (float64 stays float64), others as float64.  Above DUMP_BYTES_MAX in all, every array
+    of more than DUMP_WHOLE elements is cut to the same fraction of its elements at indices drawn from a fixed seed, so two builds
+    write the same sample."""
+    arrays = {"loss_scalars": scalars.detach().reshape(-1)}
+    for prefix, net in nets.items():
+        arrays.update({f"{prefix}.{k}": v.detach() for k, v in net.state_dict().items()})
+    host = {}
+    for name, t in arrays.items():
+        t = t.cpu().contiguous()
+        host[name] = t.numpy().astype(np.float64 if t.dtype == torch.float64 or not t.is_floating_point() else np.float32)
+    total = sum(a.nbytes for a in host.values())
+    small = sum(a.nbytes for a in host.values() if a.size <= DUMP_WHOLE)
+    frac = (DUMP_BYTES_MAX - small) / (total - small) if total > DUMP_BYTES_MAX else 1.0
+    rng = np.random.default_rng(DUMP_SAMPLE_SEED)
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in host.items():
+        if frac < 1.0 and a.size > DUMP_WHOLE:
+            a = a.reshape(-1)[np.sort(rng.choice(a.size, int(a.size * frac), replace=False))]
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    log(f"dumped {len(host)} arrays ({total / 1e6:.1f} MB{'' if frac == 1.0 else f', sampled to {frac:.3f}'}) to {out_dir}")
 
 
 def _events(st, launch, reps=20, warm=3):
@@ -544,8 +577,7 @@ def measure_dist_overhead(args, plain_ms):
     env = dict(os.environ, SMSUT_FORCE_DIST="1", MASTER_ADDR="127.0.0.1", MASTER_PORT=str(_free_port()), RANK="0", WORLD_SIZE="1",
                LOCAL_RANK=os.environ.get("LOCAL_RANK", "0"))
     env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
-    cmd = [sys.executable, os.path.abspath(__file__), "--steps", str(args.steps), "--warmup", str(args.warmup), "--no-cpu-baseline",
-           "--no-roofline", "--no-unet-step", "--no-config5", "--no-dist-leg"]
+    cmd = [sys.executable, os.path.abspath(__file__), "--steps", str(args.steps), "--warmup", str(args.warmup)]   # a plain run
     try:
         r = subprocess.run(cmd, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600)
         line = json.loads(r.stdout.decode().strip().splitlines()[-1])
@@ -567,6 +599,11 @@ def main():
     ap.add_argument("--dtype", choices=("f32", "f16"), default="f32",
                     help="conv operand dtype: f16 = BASELINE config 5's fp16 MFMA conv path (fp32 tensors / accumulators / IN / losses)")
     ap.add_argument("--size", type=int, default=256, help="slice size (config 5: 512)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last step's loss scalars and the trained weights as DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the side legs: end-to-end loops, roofline legs, per-shape step profile, U-Net step, config 5, "
+                         "data-parallel overhead, CPU baseline (the --no-* options below switch single legs off)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-roofline", action="store_true")
     ap.add_argument("--no-unet-step", action="store_true", help="skip the BASELINE config-2 (U-Net step) leg")
@@ -682,50 +719,54 @@ def main():
         t = torch.tensor([dt], dtype=torch.float64, device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
-    # ---- end to end ("report both"): the same iteration WITH the host reading its scalars back every step, as the
-    # reference's loop does (11 .item() syncs per iteration, trainer/uganConsisTrainer.py:148-149,157,183-188; here ONE 40-byte
-    # fetch of the ten scalars the iteration returns, trainer/uganConsisTrainer.py train_epoch) -- the host cannot run ahead of the
-    # device.  A second timed loop over the same resident batches (cyclically), every rank takes part (collectives).
-    e2e_steps = min(args.steps, 20)
-    torch.cuda.synchronize()
-    if world > 1:
-        dist.barrier()
-    t1 = time.perf_counter()
-    for i in range(e2e_steps):
-        b = batches[(args.warmup + i) % len(batches)]
-        r = tr.train_iteration(*b) if args.workload == "ugan" else tr.train_step(*b)
-        r.reshape(-1).tolist()                               # device -> host fetch + sync, every iteration
-    torch.cuda.synchronize()
-    if world > 1:
-        dist.barrier()
-    dt_e2e = time.perf_counter() - t1
-    if world > 1:
-        t = torch.tensor([dt_e2e], dtype=torch.float64, device=dev)
-        dist.all_reduce(t, op=dist.ReduceOp.MAX)
-        dt_e2e = float(t.item())
-    # ... and the trainers' own way of doing it (misc.utils.ScalarFetcher, trainer.train_epoch): the scalars of iteration i go to
-    # pinned memory with a non-blocking copy and are read one iteration later -- every value reaches the host, nothing stalls
-    from smsut_amd.misc.utils import ScalarFetcher
-    torch.cuda.synchronize()
-    if world > 1:
-        dist.barrier()
-    fetch = ScalarFetcher(10 if args.workload == "ugan" else 1, dev)
-    got = 0
-    t2 = time.perf_counter()
-    for i in range(e2e_steps):
-        b = batches[(args.warmup + i) % len(batches)]
-        r = tr.train_iteration(*b) if args.workload == "ugan" else tr.train_step(*b)
-        got += fetch.push(r.reshape(-1)) is not None
-    got += fetch.flush() is not None
-    torch.cuda.synchronize()
-    if world > 1:
-        dist.barrier()
-    dt_pipe = time.perf_counter() - t2
-    assert got == e2e_steps
-    if world > 1:
-        t = torch.tensor([dt_pipe], dtype=torch.float64, device=dev)
-        dist.all_reduce(t, op=dist.ReduceOp.MAX)
-        dt_pipe = float(t.item())
+    # the weights every rank holds are the same after the all-reduced step: rank 0 writes them (before any further iteration)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, last, {"net": tr.net, "D": tr.D} if args.workload == "ugan" else {"net": tr.net})
+    if args.full:
+        # ---- end to end ("report both"): the same iteration WITH the host reading its scalars back every step, as the
+        # reference's loop does (11 .item() syncs per iteration, trainer/uganConsisTrainer.py:148-149,157,183-188; here ONE 40-byte
+        # fetch of the ten scalars the iteration returns, trainer/uganConsisTrainer.py train_epoch) -- the host cannot run ahead of
+        # the device.  A second timed loop over the same resident batches (cyclically), every rank takes part (collectives).
+        e2e_steps = min(args.steps, 20)
+        torch.cuda.synchronize()
+        if world > 1:
+            dist.barrier()
+        t1 = time.perf_counter()
+        for i in range(e2e_steps):
+            b = batches[(args.warmup + i) % len(batches)]
+            r = tr.train_iteration(*b) if args.workload == "ugan" else tr.train_step(*b)
+            r.reshape(-1).tolist()                               # device -> host fetch + sync, every iteration
+        torch.cuda.synchronize()
+        if world > 1:
+            dist.barrier()
+        dt_e2e = time.perf_counter() - t1
+        if world > 1:
+            t = torch.tensor([dt_e2e], dtype=torch.float64, device=dev)
+            dist.all_reduce(t, op=dist.ReduceOp.MAX)
+            dt_e2e = float(t.item())
+        # ... and the trainers' own way of doing it (misc.utils.ScalarFetcher, trainer.train_epoch): the scalars of iteration i go to
+        # pinned memory with a non-blocking copy and are read one iteration later -- every value reaches the host, nothing stalls
+        from smsut_amd.misc.utils import ScalarFetcher
+        torch.cuda.synchronize()
+        if world > 1:
+            dist.barrier()
+        fetch = ScalarFetcher(10 if args.workload == "ugan" else 1, dev)
+        got = 0
+        t2 = time.perf_counter()
+        for i in range(e2e_steps):
+            b = batches[(args.warmup + i) % len(batches)]
+            r = tr.train_iteration(*b) if args.workload == "ugan" else tr.train_step(*b)
+            got += fetch.push(r.reshape(-1)) is not None
+        got += fetch.flush() is not None
+        torch.cuda.synchronize()
+        if world > 1:
+            dist.barrier()
+        dt_pipe = time.perf_counter() - t2
+        assert got == e2e_steps
+        if world > 1:
+            t = torch.tensor([dt_pipe], dtype=torch.float64, device=dev)
+            dist.all_reduce(t, op=dist.ReduceOp.MAX)
+            dt_pipe = float(t.item())
     dist_info = {"initialized": bool(dist.is_available() and dist.is_initialized())}
     if dist_info["initialized"]:
         dist_info.update(backend=dist.get_backend(), world_size=dist.get_world_size(), rank=dist.get_rank())
@@ -747,17 +788,18 @@ def main():
            "config": {"workload": workload, "per_gpu_batch": B, "global_batch": B * world,
                       "parallelism": f"dp{world}", "weights": "random init (reference initialisers)"},
            "last_step_scalars": [round(float(v), 5) for v in (last.reshape(-1).tolist() if last is not None else [])],
-           "end_to_end_ms_per_step": round(dt_e2e / e2e_steps * 1e3, 3),
-           "end_to_end": {"steps": e2e_steps, "ms_per_step": round(dt_e2e / e2e_steps * 1e3, 3),
-                          "slices_per_s": round(B * world * e2e_steps / dt_e2e, 3),
-                          "pipelined_fetch_ms_per_step": round(dt_pipe / e2e_steps * 1e3, 3),
-                          "pipelined_fetch_slices_per_s": round(B * world * e2e_steps / dt_pipe, 3),
-                          "pipelined_fetch": "what trainer.train_epoch does: every iteration's scalars reach the host through pinned memory "
-                                             "one iteration late (misc.utils.ScalarFetcher), no device stall",
-                          "what": "the timed iteration plus a device -> host fetch of its scalars every step (the reference reads 11 "
-                                  ".item() values per iteration, uganConsisTrainer.py:148-149,157,183-188); ms_per_step above syncs once, "
-                                  "after the last step"},
            "dist": dist_info}
+    if args.full:
+        out["end_to_end_ms_per_step"] = round(dt_e2e / e2e_steps * 1e3, 3)
+        out["end_to_end"] = {"steps": e2e_steps, "ms_per_step": round(dt_e2e / e2e_steps * 1e3, 3),
+                             "slices_per_s": round(B * world * e2e_steps / dt_e2e, 3),
+                             "pipelined_fetch_ms_per_step": round(dt_pipe / e2e_steps * 1e3, 3),
+                             "pipelined_fetch_slices_per_s": round(B * world * e2e_steps / dt_pipe, 3),
+                             "pipelined_fetch": "what trainer.train_epoch does: every iteration's scalars reach the host through pinned "
+                                                "memory one iteration late (misc.utils.ScalarFetcher), no device stall",
+                             "what": "the timed iteration plus a device -> host fetch of its scalars every step (the reference reads 11 "
+                                     ".item() values per iteration, uganConsisTrainer.py:148-149,157,183-188); ms_per_step above syncs "
+                                     "once, after the last step"}
     log(f"timed region done: {ms:.2f} ms/step")
     out["graph"] = tr.graph_report()
     # converting copies ops.nhwc()/hwio() had to make inside the timed region (0 = every tensor arrived in the kernels' layout;
@@ -797,7 +839,7 @@ def main():
     if args.dtype == "f16":
         out["whole_step"]["note_f16"] = ("fp16-operand convolutions are HBM-bound (the fp16 dense MFMA peak is 16x the fp32 one): "
                                          "the fp32-MFMA fraction above is a common yardstick with the f32 run, not this path's roofline")
-    if not args.no_roofline:
+    if args.full and not args.no_roofline:
         if args.dtype == "f16":
             out["roofline"] = measure_dominant_conv(dev, B, args.size, True)
         else:
@@ -825,16 +867,16 @@ def main():
                                                 "PMC traffic of profiles/*_step_*_classes.md stands against (SURVEY 8d's rule, call by call)")
             # the roofline leg's call is one the timed step makes (entry point + integer / float arguments)
             out["roofline"]["in_step_record"] = bool(prof.get("has_call", {}).get("dominant"))
-    if world == 1 and args.workload == "ugan" and not args.no_unet_step and args.dtype == "f32" and args.size == 256:
+    if args.full and world == 1 and args.workload == "ugan" and not args.no_unet_step and args.dtype == "f32" and args.size == 256:
         out["unet_step"] = time_unet_step(dev, rank)
         if not args.no_config5:
             out["config5"] = time_config5(dev, rank)
-    if world == 1 and args.workload == "ugan" and args.dtype == "f32" and args.size == 256 and not args.no_dist_leg \
+    if args.full and world == 1 and args.workload == "ugan" and args.dtype == "f32" and args.size == 256 and not args.no_dist_leg \
             and not parallel.force_dist():
         out["dist_overhead"] = measure_dist_overhead(args, ms)
         if "ms" in out["dist_overhead"]:
             out["dist_overhead_ms"] = out["dist_overhead"]["ms"]
-    if world == 1 and not args.no_cpu_baseline and args.size == 256:
+    if args.full and world == 1 and not args.no_cpu_baseline and args.size == 256:
         out["cpu_baseline"] = cpu_baseline_ugan() if args.workload == "ugan" else cpu_baseline_unet()
     print(json.dumps(out), flush=True)
     if world > 1:

@@ -13,12 +13,12 @@ out=gpurun_out
 common="--output-format csv"
 if [ "$part" != "2" ]; then
 rm -rf $out/${tag}_ugan $out/${tag}_unet $out/${tag}_roof $out/${tag}_pmc_fetch $out/${tag}_pmc_write
-rocprofv3 --kernel-trace --stats $common -d $out/${tag}_ugan -- python3 bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-roofline --no-unet-step --no-dist-leg > $out/${tag}_ugan.log 2>&1
+rocprofv3 --kernel-trace --stats $common -d $out/${tag}_ugan -- python3 bench.py --full --steps 5 --warmup 2 --no-cpu-baseline --no-roofline --no-unet-step --no-dist-leg > $out/${tag}_ugan.log 2>&1
 tail -1 $out/${tag}_ugan.log | cut -c1-160
-rocprofv3 --kernel-trace --stats $common -d $out/${tag}_unet -- python3 bench.py --workload unet --steps 5 --warmup 2 --no-cpu-baseline --no-roofline --no-unet-step > $out/${tag}_unet.log 2>&1
+rocprofv3 --kernel-trace --stats $common -d $out/${tag}_unet -- python3 bench.py --full --workload unet --steps 5 --warmup 2 --no-cpu-baseline --no-roofline --no-unet-step > $out/${tag}_unet.log 2>&1
 tail -1 $out/${tag}_unet.log | cut -c1-160
 rm -rf $out/${tag}_c5
-rocprofv3 --kernel-trace --stats $common -d $out/${tag}_c5 -- python3 bench.py --dtype f16 --size 512 --steps 5 --warmup 2 --no-cpu-baseline --no-roofline --no-unet-step --no-config5 > $out/${tag}_c5.log 2>&1
+rocprofv3 --kernel-trace --stats $common -d $out/${tag}_c5 -- python3 bench.py --full --dtype f16 --size 512 --steps 5 --warmup 2 --no-cpu-baseline --no-roofline --no-unet-step --no-config5 > $out/${tag}_c5.log 2>&1
 tail -1 $out/${tag}_c5.log | cut -c1-160
 rocprofv3 --kernel-trace --stats $common -d $out/${tag}_roof -- python3 bench.py --roofline-only > $out/${tag}_roof.log 2>&1
 tail -1 $out/${tag}_roof.log | cut -c1-400
@@ -37,8 +37,8 @@ fi
 if [ "$part" = "1" ]; then exit 0; fi
 # 3b. algorithmic bytes of the step's launches (bench.py's per-shape census: every tensor of every conv / InstanceNorm / tail / pooling
 #     call read once + written once), un-profiled: the floor the PMC traffic below stands against
-python3 bench.py --steps 3 --warmup 2 --no-cpu-baseline --no-unet-step --no-dist-leg --no-config5 > $out/${tag}_bytes_ugan.log 2>/dev/null
-python3 bench.py --workload unet --steps 3 --warmup 2 --no-cpu-baseline --no-unet-step > $out/${tag}_bytes_unet.log 2>/dev/null
+python3 bench.py --full --steps 3 --warmup 2 --no-cpu-baseline --no-unet-step --no-dist-leg --no-config5 > $out/${tag}_bytes_ugan.log 2>/dev/null
+python3 bench.py --full --workload unet --steps 3 --warmup 2 --no-cpu-baseline --no-unet-step > $out/${tag}_bytes_unet.log 2>/dev/null
 # 4. whole-step counters per layer class (profiles/step_pmc.py: eager steps between two marker dispatches; four passes each:
 #    durations without counters, FETCH_SIZE, WRITE_SIZE, SQ) -> profiles/<tag>_step_<wl>_classes.{json,md}
 for wl in unet ugan; do

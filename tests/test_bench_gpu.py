@@ -56,3 +56,36 @@ def test_roofline_legs_are_calls_of_the_recorded_iteration(monkeypatch):
     assert r["entry_point"] == name and r["avg_launch_ms"] > 0 and r["call_ms_with_reduction"] >= r["avg_launch_ms"]
     f = bench.measure_dominant_conv(torch.device("cuda"), B, 256)
     assert f["entry_point"] == "smsut_conv2d_fwd_mfma_stats_sc_fin" and f["executed_mfma_tflops"] <= f["achieved"]
+
+
+def _plain_run(out_dir):
+    import json
+    import subprocess
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "2", "--per-gpu-batch", "4",
+           "--dump-outputs", str(out_dir)]
+    r = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    return json.loads(r.stdout.strip().splitlines()[-1])
+
+
+def test_plain_run_is_the_headline_and_dumps_its_last_step(tmp_path):
+    """A plain ``bench.py`` run times exactly ``--steps`` steps and prints the headline without the side legs of ``--full``;
+    ``--dump-outputs`` writes the last timed step's loss scalars and the trained weights, the same ones for the same arguments."""
+    import numpy as np
+    lines = [_plain_run(tmp_path / "a"), _plain_run(tmp_path / "b")]
+    for line in lines:
+        assert line["steps"] == 3 and line["ms_per_step"] > 0 and line["higher_is_better"] is True
+        assert line["metric"].startswith("slices/sec uganConsisTrainer step") and line["unit"] == "slices/s" and line["dtype"] == "f32"
+        assert abs(line["value"] - 4 * 1e3 / line["ms_per_step"]) <= 1e-3 * line["value"] + 0.01
+        assert not {"end_to_end", "roofline", "unet_step", "config5", "dist_overhead", "cpu_baseline"} & set(line)
+    names = sorted(p.name for p in (tmp_path / "a").iterdir())
+    assert names == sorted(p.name for p in (tmp_path / "b").iterdir())
+    assert "loss_scalars.npy" in names and any(n.startswith("net.") for n in names) and any(n.startswith("D.") for n in names)
+    assert sum((tmp_path / "a" / n).stat().st_size for n in names) <= 64e6
+    scal = np.load(tmp_path / "a" / "loss_scalars.npy")
+    assert scal.dtype == np.float32 and scal.shape == (10,) and np.isfinite(scal).all()
+    np.testing.assert_allclose(scal, lines[0]["last_step_scalars"], rtol=1e-4, atol=1e-5)
+    for n in names:
+        a, b = np.load(tmp_path / "a" / n), np.load(tmp_path / "b" / n)
+        assert a.dtype in (np.float32, np.float64) and a.shape == b.shape, n
+        np.testing.assert_allclose(a, b, rtol=1e-5, atol=1e-6, err_msg=n)
