@@ -13,7 +13,10 @@
  *     are [kh][kw][Cin][Cout]; Linear weights are [in][out];
  *   - `stream` is a hipStream_t passed as void*; every kernel is enqueued on it (graph-capture safe);
  *   - return value: 0 = enqueued, -1 = invalid argument, > 0 = hipError_t of the launch; nothing throws;
- *   - no global mutable state; safe to call from several host threads on different streams.
+ *   - no global mutable state; safe to call from several host threads on different streams;
+ *   - the library's only environment input is SMSUT_WINOGRAD, read once per process: "0" runs the direct forms of
+ *     the 3x3 convs where the Winograd F(2x2,3x3) forms would run (the reference those forms are tested against);
+ *     every other kernel choice follows from the arguments of the call.
  */
 #ifndef SMSUT_HIP_H
 #define SMSUT_HIP_H

@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <stdlib.h>
 
 #define SMSUT_OK 0
 #define SMSUT_EINVAL (-1)
@@ -18,6 +19,23 @@
   } while (0)
 
 static inline int64_t cdiv64(int64_t a, int64_t b) { return (a + b - 1) / b; }
+
+// CUs of the current device: the persistent grids are sized for one resident round on all of them
+inline int device_cus() {
+  static const int cus = [] {
+    int dev = 0, n = 256;
+    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) n = 256;
+    return n > 0 ? n : 256;
+  }();
+  return cus;
+}
+
+// SMSUT_WINOGRAD=0 runs the direct forms of the 3x3 convs where the Winograd ones would run: the reference the Winograd forms are
+// tested against (tests/test_winograd_evidence_gpu.py).  The library's only environment input, read once per process.
+inline bool winograd_on() {
+  static const bool on = [] { const char* e = getenv("SMSUT_WINOGRAD"); return !e || atoi(e) != 0; }();
+  return on;
+}
 
 // grid-stride launch width for memory-bound elementwise kernels: 256 CUs x 8 blocks (guide G11)
 #ifndef SMSUT_EW_GRID_CAP

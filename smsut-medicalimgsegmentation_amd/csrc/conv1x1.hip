@@ -460,13 +460,12 @@ int smsut_conv1x1_fwd_split(const float* x, const float* w, float* ya, float* yb
 }
 
 // ConvTranspose2d(k=2, s=2, bias=False) through the 1x1 kernels' pixel-shuffle forms (see conv1x1_fwd / conv1x1_wgrad, PS):
-// x [N,H,W,Cin], w [2][2][Cin][Cout], y / gy [N,2H,2W,Cout].  Cout % 16 == 0, Cin % 4 == 0.  SMSUT_CONVT_PS=0/1.
+// x [N,H,W,Cin], w [2][2][Cin][Cout], y / gy [N,2H,2W,Cout].  Cout % 16 == 0, Cin % 4 == 0.
 int smsut_convT2x2_ps_supported(int Cin, int Cout) {
-  static const bool on = [] { const char* e = getenv("SMSUT_CONVT_PS"); return !e || atoi(e) != 0; }();
   // Cout == 16 only (the 128^2 -> 256^2 level): there the four taps are one 64-column slab -- 32x128^2 32->16: forward 66.4 ->
   // 62.1 us, weight gradient 91.4 -> 53.2 us; from 32 output channels on the per-tap MFMA kernels win (64->32: 38.6 / 42.2 and
   // 48.2 / 49.8 us; 128->64: 32.2 / 34.1 and 40.4 / 49.0) -- scratch/convt_probe.py.  The kernels take any Cout % 16 == 0.
-  return on && Cout == 16 && smsut_conv1x1_supported(Cin, 4 * Cout);
+  return Cout == 16 && smsut_conv1x1_supported(Cin, 4 * Cout);
 }
 
 int smsut_convT2x2_fwd_ps(const float* x, const float* w, float* y, int N, int H, int W, int Cin, int Cout, void* stream) {

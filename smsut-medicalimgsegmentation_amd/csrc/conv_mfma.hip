@@ -26,7 +26,6 @@
 #include "conv_wino.h"
 #include "conv_wgrad_rr.h"
 #include <stdlib.h>
-#include <stdio.h>
 #include <type_traits>
 
 namespace {
@@ -1957,10 +1956,9 @@ int launch_fwd(const float* x, const float* w, float* y, int N, int H, int W, in
       (y2 && (osc != 1 || ntap_out != 1 || stats || split <= 0 || split >= Ndim || split % 16 != 0)))
     return -1;
   if constexpr (KS == 3 && MW == TW && SMSUT_F16_X32) {
-    // SMSUT_F16_CK32=0: 16-channel passes (A/B; config 5 49.50 -> 48.56 ms with 32-channel passes on every tile shape, 48.95 with
-    // them on the 16-row tiles only)
-    static const bool ck32 = [] { const char* e = getenv("SMSUT_F16_CK32"); return !e || atoi(e) != 0; }();
-    if (f16 && ck32 && Kdim % 32 == 0 && Kdim >= 32 && (!x2 || (Kdim / 2) % 32 == 0) && isc == 1 && osc == 1 && G == 1) {
+    // 32-channel passes on every tile shape (config 5: 49.50 ms with 16-channel passes -> 48.56 ms, 48.95 with 32-channel passes on
+    // the 16-row tiles only)
+    if (f16 && Kdim % 32 == 0 && Kdim >= 32 && (!x2 || (Kdim / 2) % 32 == 0) && isc == 1 && osc == 1 && G == 1) {
       conv_mfma_fwd<KS, TH, WM, WN, NTN, true, MW, 32><<<grid, TPB, sh32, st>>>(x, w, y, H, W, Kdim, Ndim, tiles_x, transposed, isc,
                                                                               osc, G, nz, stats, x2, y2, split, gsc);
       return 0;
@@ -1973,20 +1971,6 @@ int launch_fwd(const float* x, const float* w, float* y, int N, int H, int W, in
     conv_mfma_fwd<KS, TH, WM, WN, NTN, false, MW><<<grid, TPB, sh, st>>>(x, w, y, H, W, Kdim, Ndim, tiles_x, transposed, isc,
                                                                          osc, G, nz, stats, x2, y2, split);
   return 0;
-}
-
-inline int device_cus() {
-  static const int cus = [] {
-    // SMSUT_CUS: the number of CUs the persistent grids are sized for, when the launch stream owns fewer than the device has (a CU
-    // mask: trainer SMSUT_CU_SPLIT keeps a few CUs for the discriminator's side stream) -- tuning hook
-    if (const char* e = getenv("SMSUT_CUS")) { const int v = atoi(e); if (v > 0) return v; }
-    int dev = 0, n = 256;
-    if (hipGetDevice(&dev) != hipSuccess ||
-        hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
-      n = 256;
-    return n > 0 ? n : 256;
-  }();
-  return cus;
 }
 
 // Persistent variant: LDS bytes and eligibility (see conv_mfma_fwd_p).
@@ -2049,13 +2033,12 @@ int launch_fwd_p(const float* x, const float* w, float* y, int N, int H, int W, 
   const int nz = N8 ? 1 : Ndim / (16 * NTN);
   // The persistent grid is sized for ONE resident round of the kernel instantiation ACTUALLY launched, at its own dynamic LDS size
   // (P_K below; ADVICE r04: one occupancy figure -- the fp32 statistics form's -- used to serve every form of this template, whatever
-  // its registers and LDS: fused shortcut, fp16 operands, half storage).  Tuning hook: SMSUT_P_WGS_PER_CU overrides the count.
-  static const int occ_env = [] { const char* e = getenv("SMSUT_P_WGS_PER_CU"); return e ? atoi(e) : 0; }();
+  // its registers and LDS: fused shortcut, fp16 operands, half storage).
   const int64_t items = (int64_t)N * tiles_img;
   int ipw = 1;
   dim3 grid(1, nz);
   auto size_grid = [&](int occ) {
-    const int64_t slots = (int64_t)device_cus() * (occ_env > 0 ? occ_env : occ);
+    const int64_t slots = (int64_t)device_cus() * occ;
     ipw = (int)((items * nz + slots - 1) / slots);        // one resident round: each workgroup walks ipw consecutive items
     if (ipw < 1) ipw = 1;
     grid.x = (unsigned)((items + ipw - 1) / ipw);
@@ -2208,19 +2191,16 @@ int launch_fwd_p(const float* x, const float* w, float* y, int N, int H, int W, 
 }
 
 // shapes the persistent kernel takes (3x3 regular conv): resident weight block fits, full tiles, enough items to fill
-// one resident round.  SMSUT_CONV_PERSISTENT=0 keeps the per-tile kernel (A/B switch).
+// one resident round
 inline bool fwd_p_eligible(int N, int H, int W, int Kdim, int Ndim) {
-  static const bool use_p = [] { const char* e = getenv("SMSUT_CONV_PERSISTENT"); return !e || atoi(e) != 0; }();
-  static const bool use_k8 = [] { const char* e = getenv("SMSUT_CONV_K8"); return !e || atoi(e) != 0; }();
-  return use_p && (Kdim == 16 || Kdim == 32 || Kdim == 64 || (Kdim == 8 && use_k8)) && W % TW == 0 && H % 8 == 0 && Ndim % 16 == 0 &&
+  return (Kdim == 8 || Kdim == 16 || Kdim == 32 || Kdim == 64) && W % TW == 0 && H % 8 == 0 && Ndim % 16 == 0 &&
          (int64_t)N * (H / 8) * (W / TW) * (Ndim / 16) >= 1024 && (int64_t)N * H * W * (Kdim > Ndim ? Kdim : Ndim) < (1ll << 31);
 }
 
 // ... or the large-reduction Winograd kernel (conv_wino.hip: fp32 only, Kdim >= 64, 16x16 tiles)
+constexpr int WINO_L_MIN_K = 64;
 inline bool wino_l_shape(int N, int H, int W, int Kdim, int Ndim) {
-  static const bool use_wino = [] { const char* e = getenv("SMSUT_WINOGRAD"); return !e || atoi(e) != 0; }();
-  static const int min_k = [] { const char* e = getenv("SMSUT_WINO_L_MIN_K"); return e ? atoi(e) : 64; }();   // (tuning hook)
-  return use_wino && Kdim >= min_k && smsut_wino_l_eligible(N, H, W, Kdim, Ndim);
+  return winograd_on() && Kdim >= WINO_L_MIN_K && smsut_wino_l_eligible(N, H, W, Kdim, Ndim);
 }
 inline bool fwd_any_eligible(int N, int H, int W, int Kdim, int Ndim, bool f16) {
   return fwd_p_eligible(N, H, W, Kdim, Ndim) || (!f16 && wino_l_shape(N, H, W, Kdim, Ndim));
@@ -2254,17 +2234,15 @@ inline int select_fwd_p(const float* x, const float* w, float* y, int N, int H, 
   }
   if (Kdim == 8) return (H % 16 == 0) ? launch_fwd_p<3, 16, 1, 1, true>(PARGS) : launch_fwd_p<3, 8, 1, 1, true>(PARGS);
   // Winograd F(2x2,3x3) form (r03: 1.2-1.4x the direct form on these shapes, scratch/wino_probe.py): every fp32 form of the
-  // 16- and 32-channel reductions on 16-row items.  SMSUT_WINOGRAD=0 keeps the direct forms (A/B switch).  Chosen by SHAPE
-  // only, never by form, so that the forms of one shape stay bit-identical to each other (virtual cat vs materialised, fused
-  // shortcut vs plain, input-side IN vs applied).
-  static const bool use_wino = [] { const char* e = getenv("SMSUT_WINOGRAD"); return !e || atoi(e) != 0; }();
-  if (use_wino && !f16 && H % 16 == 0 && (Kdim == 16 || Kdim == 32))
+  // 16- and 32-channel reductions on 16-row items (winograd_on(): the direct forms are the reference).  Chosen by SHAPE only,
+  // never by form, so that the forms of one shape stay bit-identical to each other (virtual cat vs materialised, fused shortcut vs
+  // plain, input-side IN vs applied).
+  if (winograd_on() && !f16 && H % 16 == 0 && (Kdim == 16 || Kdim == 32))
     return Kdim == 16 ? launch_fwd_p<3, 16, 1, 1, false, false, true>(PARGS) : launch_fwd_p<3, 16, 1, 2, false, false, true>(PARGS);
   if (Kdim == 16 && H % 16 == 0) return launch_fwd_p<3, 16, 1, 1>(PARGS);
-  // (tuning hook SMSUT_F16_TH16, off: 16-row items re-read 1.27x their input as halo instead of 1.41x, but the halo rows are L2 hits
-  //  under the XCD-aware item map -- config 5 measured 52.77 ms off, 52.80 with 1 (Ndim 16 only), 53.59 with 2 (every Kdim-32 shape))
-  static const int f16_th16 = [] { const char* e = getenv("SMSUT_F16_TH16"); return e ? atoi(e) : 0; }();
-  if (f16 && f16_th16 && Kdim == 32 && H % 16 == 0 && (f16_th16 > 1 || Ndim % 32 != 0)) return launch_fwd_p<3, 16, 1, 2>(PARGS);
+  // (fp16 operands, Kdim 32 stay on 8-row items: 16-row items re-read 1.27x their input as halo instead of 1.41x, but the halo rows
+  //  are L2 hits under the XCD-aware item map -- config 5 measured 52.77 ms on 8-row items, 52.80 with 16-row items for Ndim 16 only,
+  //  53.59 with them on every Kdim-32 shape)
   if (Kdim == 32 && Ndim % 32 == 0 && !(y2 && split % 32 != 0)) return launch_fwd_p<3, 8, 2, 2>(PARGS);   // (32-channel slabs must not straddle a split)
   if (Kdim == 16) return launch_fwd_p<3, 8, 1, 1>(PARGS);
   if (Kdim == 32) return launch_fwd_p<3, 8, 1, 2>(PARGS);
@@ -2273,10 +2251,9 @@ inline int select_fwd_p(const float* x, const float* w, float* y, int N, int H, 
   return -1;
 }
 
-// 8-channel results on the persistent kernel (data-gradient of the first block after the stem).  SMSUT_CONV_N8=0/1.
+// 8-channel results on the persistent kernel (data-gradient of the first block after the stem)
 inline bool fwd_p_n8_eligible(int N, int H, int W, int Kdim, int Ndim) {
-  static const bool on = [] { const char* e = getenv("SMSUT_CONV_N8"); return !e || atoi(e) != 0; }();
-  return on && Ndim == 8 && (Kdim == 16 || Kdim == 32) && W % TW == 0 && H % 8 == 0 && (int64_t)N * (H / 8) * (W / TW) >= 1024 &&
+  return Ndim == 8 && (Kdim == 16 || Kdim == 32) && W % TW == 0 && H % 8 == 0 && (int64_t)N * (H / 8) * (W / TW) >= 1024 &&
          (int64_t)N * H * W * Kdim < (1ll << 31);
 }
 
@@ -2288,13 +2265,9 @@ int dispatch_fwd(const float* x, const float* w, float* y, int N, int H, int W, 
 #define ARGS x, w, y, N, H, W, Kdim, Ndim, transposed, isc, osc, G, ntap_out, st, stats, tiles_out, x2, y2, split, f16, gsc
   // From the r01 sweep (scratch/bench_conv.py, B=32, U-Net shapes): 8-row tiles win everywhere; 32 output channels
   // per workgroup (grid.z walks the rest) beat 64, and 16 win when the grid would otherwise be < ~4 WGs per CU.
-  static const bool log_shapes = getenv("SMSUT_LOG_CONV") != nullptr;      // shape census for tuning (stderr)
-  if (log_shapes && !tiles_out)
-    fprintf(stderr, "[conv] KS %d N %d H %d W %d K %d N %d tr %d isc %d osc %d G %d p3 %d\n", KS, N, H, W, Kdim, Ndim,
-            transposed, isc, osc, G, (int)(KS == 3 && isc == 1 && osc == 1 && G == 1 && ntap_out == 1 && fwd_p_eligible(N, H, W, Kdim, Ndim)));
   if constexpr (KS == 3) {
     // small-Cin / large-image layers: persistent kernel with resident weights (see conv_mfma_fwd_p); it declines
-    // (-1) shapes it does not cover.  SMSUT_CONV_PERSISTENT=0 keeps the per-tile kernel (A/B switch).
+    // (-1) shapes it does not cover, which fall through to the per-tile kernel below.
     if (isc == 1 && osc == 1 && G == 1 && ntap_out == 1 && fwd_any_eligible(N, H, W, Kdim, Ndim, f16)) {
       if (select_fwd_p(x, w, y, N, H, W, Kdim, Ndim, transposed, st, stats, tiles_out, nullptr, y2, split, x2, nullptr, f16,
                        gsc, nullptr, wu) == 0)
@@ -2312,11 +2285,10 @@ int dispatch_fwd(const float* x, const float* w, float* y, int N, int H, int W, 
   // planes of <= 4 rows (discriminator 4x4 level): the 4-row tile halves the rows of padding every MFMA multiplies --
   // scratch/bench_conv_small.py, 256->256: 19.4 vs 29.1 us forward, 25.1 vs 32.7 us data-gradient at B=16 (28.7 vs 48.2 at 32)
   // 8x8 planes of the discriminator's deep levels: M-tiles of real pixels only -- four (2 rows x 8 columns) tiles per plane, 16
-  // output channels per workgroup so that B=16 still gives one workgroup per CU (SMSUT_DENSE_PLANES=0: 16-wide tiles).
+  // output channels per workgroup so that B=16 still gives one workgroup per CU.
   // (4x4 planes stay on the 4-row tile: a plane is ONE M-tile, and 64-channel workgroups leave 64 of them for 256 CUs --
   //  measured 71 us vs 19-25 us; there the limit is parallelism, not padded MFMAs.)
-  static const bool dense = [] { const char* e = getenv("SMSUT_DENSE_PLANES"); return !e || atoi(e) != 0; }();
-  if (dense && isc == 1 && osc == 1 && G == 1 && ntap_out == 1 && !f16 && H <= 8 && W <= 8 && H > 4)
+  if (isc == 1 && osc == 1 && G == 1 && ntap_out == 1 && !f16 && H <= 8 && W <= 8 && H > 4)
     return launch_fwd<KS, 8, 4, 1, 1, 8>(ARGS);
   if (H <= 4 && isc == 1 && osc == 1) return launch_fwd<KS, 4, 4, 1, 1>(ARGS);
   if (nt == 1) return launch_fwd<KS, 8, 4, 1, 1>(ARGS);
@@ -2332,9 +2304,7 @@ int dispatch_fwd(const float* x, const float* w, float* y, int N, int H, int W, 
 template <int KS>
 int dispatch_fwd_cfg(int cfg, const float* x, const float* w, float* y, int N, int H, int W, int Kdim, int Ndim,
                      int transposed, hipStream_t st) {
-  // (SMSUT_CFG_F16=1: the fp16-operand instantiations of the same tile shapes -- the sweep behind dispatch_fwd's fp16 table)
-  static const bool cfg_f16 = [] { const char* e = getenv("SMSUT_CFG_F16"); return e && atoi(e) != 0; }();
-#define ARGS x, w, y, N, H, W, Kdim, Ndim, transposed, 1, 1, 1, 1, st, nullptr, nullptr, nullptr, nullptr, 0, cfg_f16
+#define ARGS x, w, y, N, H, W, Kdim, Ndim, transposed, 1, 1, 1, 1, st
   switch (cfg) {
     case 0: return launch_fwd<KS, 16, 4, 1, 1>(ARGS);
     case 1: return launch_fwd<KS, 8, 4, 1, 1>(ARGS);
@@ -2676,6 +2646,10 @@ conv_k4_wgrad(const float* __restrict__ x, const float* __restrict__ gy, float* 
 
 struct WgradPlan { int cit, cot, splits, tiles_per_split, tiles_x, tiles_y; };
 
+constexpr int WGRAD_TARGET11 = 768;     // workgroups the split plan aims for: 16 x 16 slabs ...
+constexpr int WGRAD_TARGET = 512;       // ... and the wider ones
+constexpr int WGRAD_CAP_MFLOATS = 8;    // bound on the split slabs sum_splits re-reads (M floats)
+
 WgradPlan plan_wgrad(int N, int H, int W, int Cin, int Cout) {
   WgradPlan p;
   // (2x2 slabs need 178 VGPRs + 144 AGPRs = one wave per SIMD, yet measured faster than 2x1 / 1x2 slabs at two waves
@@ -2689,15 +2663,12 @@ WgradPlan plan_wgrad(int N, int H, int W, int Cin, int Cout) {
   // PMC (r01, 64->64 @64^2): with 1024 two-tile workgroups the kernel averaged < 1 resident wave per SIMD -- the
   // per-workgroup fixed cost (descriptor setup, first-tile latency, cross-wave combine, slab store) dominated.  The
   // 144..186-VGPR variants fit 2 workgroups per CU, so ONE resident round of 512 workgroups with more tiles each.
-  static const int t11 = [] { const char* e = getenv("SMSUT_WGRAD_TARGET11"); return e ? atoi(e) : 768; }();   // (tuning hooks)
-  static const int t22 = [] { const char* e = getenv("SMSUT_WGRAD_TARGET"); return e ? atoi(e) : 512; }();
-  const int target = (p.cit == 1 && p.cot == 1) ? t11 : t22;
+  const int target = (p.cit == 1 && p.cot == 1) ? WGRAD_TARGET11 : WGRAD_TARGET;
   int want = (target + slabs - 1) / slabs;
   // ... but keep the per-split slabs that sum_splits has to re-read bounded (default 32 MB = 8M floats; an 8 MB cap
   // left the 64->64 layers with 208 workgroups for 256 CUs: PMC showed < 1 resident wave per SIMD).
   const int64_t wsz = (int64_t)Cin * Cout * 9;
-  static const int cap_mfloats = [] { const char* e = getenv("SMSUT_WGRAD_CAP_MFLOATS"); return e ? atoi(e) : 8; }();
-  int cap = (int)(((int64_t)cap_mfloats << 20) / wsz);
+  int cap = (int)(((int64_t)WGRAD_CAP_MFLOATS << 20) / wsz);
   if (cap < 1) cap = 1;
   if (want > cap) want = cap;
   if (want > total) want = total;
@@ -2826,8 +2797,7 @@ int smsut_conv2d_fwd_mfma_stats_inaff(const float* x, const float* w, float* y, 
 //   smsut_conv2d_mfma_tiles(N, H, W, Kdim, Ndim, 3)).  xb != null: x is the virtual cat([x, xb]) of two [N,H,W,Kdim/2] tensors.
 // w [3][3][Kdim][Ndim], wsc [Kdim][Ndim] (HWIO).  Persistent-kernel shapes with Kdim in {16, 32, 64}: _supported says which.
 int smsut_conv2d_fwd_sc_supported(int N, int H, int W, int Kdim, int Ndim, int cat) {
-  static const bool on = [] { const char* e = getenv("SMSUT_FUSE_SHORTCUT"); return !e || atoi(e) != 0; }();
-  if (!on || N <= 0 || H <= 0 || W <= 0) return 0;
+  if (N <= 0 || H <= 0 || W <= 0) return 0;
   if (wino_l_shape(N, H, W, Kdim, Ndim)) return (!cat || Kdim % 32 == 0) ? 1 : 0;       // (conv_wino.hip: any reduction width)
   if (!(Kdim == 8 || Kdim == 16 || Kdim == 32 || Kdim == 64) || !fwd_p_eligible(N, H, W, Kdim, Ndim)) return 0;
   if (cat && Kdim % 32 != 0) return 0;
@@ -2852,8 +2822,7 @@ int smsut_conv2d_fwd_mfma_stats_sc(const float* x, const float* xb, const float*
 // ... with fp16 operands (BASELINE config 5): the persistent kernel's direct form, Kdim in {16, 32, 64} (the fp16-operand mode has
 // no Winograd forms); statistics tiles = smsut_conv2d_mfma_tiles(N, H, W, Kdim, Ndim, 3, /*f16=*/1).
 int smsut_conv2d_fwd_sc_f16_supported(int N, int H, int W, int Kdim, int Ndim, int cat) {
-  static const bool on = [] { const char* e = getenv("SMSUT_FUSE_SHORTCUT_F16"); return !e || atoi(e) != 0; }();
-  if (!on || N <= 0 || H <= 0 || W <= 0 || !(Kdim == 16 || Kdim == 32 || Kdim == 64) || !fwd_p_eligible(N, H, W, Kdim, Ndim)) return 0;
+  if (N <= 0 || H <= 0 || W <= 0 || !(Kdim == 16 || Kdim == 32 || Kdim == 64) || !fwd_p_eligible(N, H, W, Kdim, Ndim)) return 0;
   if (cat && Kdim % 32 != 0) return 0;
   return 1;
 }
@@ -2872,8 +2841,7 @@ int smsut_conv2d_fwd_mfma_stats_sc_f16(const float* x, const float* xb, const fl
 // weights [3][3][Cin][Cout], [Cin][Cout]).  gxb != null: channels [0, split) of gx go to gxa [N,H,W,split], the rest to gxb
 // (block input was cat([up, skip])).  Persistent-kernel shapes with Cout in {16, 32}: _supported says which.
 int smsut_conv2d_dgrad_sc_supported(int N, int H, int W, int Cout, int Cin, int split) {
-  static const bool on = [] { const char* e = getenv("SMSUT_FUSE_SHORTCUT_DGRAD"); return !e || atoi(e) != 0; }();
-  if (!on || N <= 0 || H <= 0 || W <= 0 || !(Cout == 16 || Cout == 32)) return 0;
+  if (N <= 0 || H <= 0 || W <= 0 || !(Cout == 16 || Cout == 32)) return 0;
   if (Cin == 8) return !split && Cout == 16 && fwd_p_n8_eligible(N, H, W, 2 * Cout, Cin);       // first block after the stem: 8-channel result
   if (!fwd_any_eligible(N, H, W, 2 * Cout, Cin, false)) return 0;
   if (split && (split <= 0 || split >= Cin || split % 16 != 0 || (Cin - split) % 16 != 0)) return 0;
@@ -2893,11 +2861,10 @@ int smsut_conv2d_dgrad_mfma_sc(const float* gy, const float* gs, const float* w,
 
 // fp16 RESULT STORAGE (config 5, r04): the same passes, the raw conv outputs y (and ysc) stored as fp16 [N,H,W,Ndim] -- block-internal
 // tensors of a BasicBlock (its consumers: smsut_restail_*_hs).  Persistent-kernel shapes, Kdim in {16, 32, 64}; xb nullable
-// (virtual cat); InstanceNorm partials as in the fp32-storage forms (tiles with f16 = 1).  SMSUT_F16_STORE=0 switches it off.
+// (virtual cat); InstanceNorm partials as in the fp32-storage forms (tiles with f16 = 1).
 // Kdim == 8 (the first block after the stem): the fused-shortcut form only, fp32 operands (no fp16 twin), same fp16 storage.
 int smsut_conv2d_f16_hs_supported(int N, int H, int W, int Kdim, int Ndim, int cat) {
-  static const bool on = [] { const char* e = getenv("SMSUT_F16_STORE"); return !e || atoi(e) != 0; }();
-  if (!on || N <= 0 || H <= 0 || W <= 0 || !fwd_p_eligible(N, H, W, Kdim, Ndim)) return 0;
+  if (N <= 0 || H <= 0 || W <= 0 || !fwd_p_eligible(N, H, W, Kdim, Ndim)) return 0;
   if (Kdim == 8) return !cat && smsut_conv2d_fwd_sc_supported(N, H, W, Kdim, Ndim, 0);
   if (!(Kdim == 16 || Kdim == 32 || Kdim == 64)) return 0;
   return !(cat && Kdim % 32 != 0);
@@ -2961,10 +2928,9 @@ int smsut_conv2d_dgrad_mfma_bwdstats_f16_hs(const float* gy, const float* w, flo
 }
 
 // ... with fp16 operands (config 5): gsc = {s, 1/s} of smsut_absmax_scale2(gy, gs) -- the two gradients share the accumulators, so
-// they share the scale.  Direct resident-weight form (16 / 32 -> Cin >= 16).  SMSUT_FUSE_SHORTCUT_DGRAD_F16=0 switches it off.
+// they share the scale.  Direct resident-weight form (16 / 32 -> Cin >= 16).
 int smsut_conv2d_dgrad_sc_f16_supported(int N, int H, int W, int Cout, int Cin, int split) {
-  static const bool on = [] { const char* e = getenv("SMSUT_FUSE_SHORTCUT_DGRAD_F16"); return !e || atoi(e) != 0; }();
-  if (!on || N <= 0 || H <= 0 || W <= 0 || !(Cout == 16 || Cout == 32) || Cin < 16 || !fwd_p_eligible(N, H, W, 2 * Cout, Cin)) return 0;
+  if (N <= 0 || H <= 0 || W <= 0 || !(Cout == 16 || Cout == 32) || Cin < 16 || !fwd_p_eligible(N, H, W, 2 * Cout, Cin)) return 0;
   if (split && (split <= 0 || split >= Cin || split % 16 != 0 || (Cin - split) % 16 != 0)) return 0;
   return 1;
 }
@@ -2988,8 +2954,7 @@ int smsut_conv2d_mfma_form(int N, int H, int W, int Kdim, int Ndim, int sc_dgrad
   const bool sc2_64 = sc_dgrad && Kdim == 64 && fwd_p_eligible(N, H, W, Kdim, Ndim);
   if (!sc2_64 && wino_l_shape(N, H, W, Kdim, Ndim)) return 2;
   if (Ndim == 8 || Kdim == 8) return 0;
-  static const bool use_wino = [] { const char* e = getenv("SMSUT_WINOGRAD"); return !e || atoi(e) != 0; }();
-  return (use_wino && H % 16 == 0 && (Kdim == 16 || Kdim == 32) && fwd_p_eligible(N, H, W, Kdim, Ndim)) ? 1 : 0;
+  return (winograd_on() && H % 16 == 0 && (Kdim == 16 || Kdim == 32) && fwd_p_eligible(N, H, W, Kdim, Ndim)) ? 1 : 0;
 }
 
 
@@ -3185,21 +3150,12 @@ int smsut_conv2d_wgrad_mfma_supported(int KS, int stride, int pad, int Cin, int 
 }
 
 // workspace floats: splits * KS*KS*Cin*Cout
-// (3x3: the Winograd weight-gradient kernel of conv_wino.hip may take the shape instead; the workspace covers either)
-inline bool wino_wg_shape(int N, int H, int W, int Cin, int Cout, const float* x2, int ca) {
-  static const bool use_wino = [] { const char* e = getenv("SMSUT_WINOGRAD"); return !e || atoi(e) != 0; }();
-  return use_wino && smsut_wino_wg_eligible(N, H, W, Cin, Cout, x2, ca);
-}
 int64_t smsut_conv2d_wgrad_mfma_ws(int N, int H, int W, int Cin, int Cout, int KS) {
   const WgradPlan p = plan_wgrad(N, H, W, Cin, Cout);
   int64_t need = (int64_t)p.splits * KS * KS * Cin * Cout;
   if (KS == 3) {                                       // the register-row kernel (conv_wgrad_rr.hip) plans its own split count
     const int64_t rr = (int64_t)smsut_wgrad_rr_splits(N, H, W, Cin, Cout, nullptr, 0, false, false) * 9 * Cin * Cout;
     if (rr > need) need = rr;
-  }
-  if (KS == 3 && wino_wg_shape(N, H, W, Cin, Cout, nullptr, 0)) {
-    const int64_t wn = smsut_wino_wg_ws(N, H, W, Cin, Cout);
-    if (wn > need) need = wn;
   }
   return need;
 }
@@ -3210,8 +3166,7 @@ int64_t smsut_conv2d_wgrad_mfma_ws(int N, int H, int W, int Cin, int Cout, int K
 #endif
 // planes small enough for the whole-batch GEMM form
 inline bool plane_wgrad_applies(int N, int H, int W, int Cin, int Cout) {
-  static const bool on = [] { const char* e = getenv("SMSUT_PLANE_WGRAD"); return !e || atoi(e) != 0; }();
-  return on && H * W <= PLANE_WGRAD_MAX_HW && W % 4 == 0 && Cin % 32 == 0 && Cout % 32 == 0 && (int64_t)N * H * W <= 4096 &&
+  return H * W <= PLANE_WGRAD_MAX_HW && W % 4 == 0 && Cin % 32 == 0 && Cout % 32 == 0 && (int64_t)N * H * W <= 4096 &&
          (int64_t)N * H * W * (Cin > Cout ? Cin : Cout) < (1ll << 31);
 }
 
@@ -3227,14 +3182,6 @@ static int wgrad_mfma_launch(const float* x, const float* gy, float* gw, float* 
   SMSUT_REQUIRE(!x2 || (ca > 0 && ca < Cin && ca % 16 == 0 && (Cin - ca) % 4 == 0));
   SMSUT_REQUIRE(!aff || (KS == 3 && !x2));
   hipStream_t st = (hipStream_t)stream;
-  if (KS == 3 && !gs && wino_wg_shape(N, H, W, Cin, Cout, x2, ca)) {     // Winograd F(3x3, 2x2): plain, virtual-cat, input-side IN
-    WinoAff wa;
-    if (aff) wa = WinoAff{aff->mean, aff->rstd, aff->gamma, aff->beta, aff->slope};
-    if (smsut_wino_wg_launch(x, x2, ca, gy, gw, workspace, N, H, W, Cin, Cout, aff ? &wa : nullptr, st) == 0) {
-      SMSUT_LAUNCH_CHECK();
-      return SMSUT_OK;
-    }
-  }
   if (KS == 3 && smsut_wgrad_rr_eligible(N, H, W, Cin, Cout, x2, ca, aff != nullptr, gs != nullptr)) {
     // register-row kernel (conv_wgrad_rr.hip): no LDS staging, no barrier in the main loop
     RrAff ra;
@@ -3258,8 +3205,7 @@ static int wgrad_mfma_launch(const float* x, const float* gy, float* gw, float* 
     SMSUT_LAUNCH_CHECK();
     return SMSUT_OK;                                 // final values written directly: no split-slab sum
   } else {
-    static const bool use_c8 = [] { const char* e = getenv("SMSUT_CONV_K8"); return !e || atoi(e) != 0; }();
-    const bool c8 = use_c8 && Cin == 8 && !x2 && !aff;                    // tap pairs share an accumulator tile
+    const bool c8 = Cin == 8 && !x2 && !aff;                    // tap pairs share an accumulator tile
     if (gs && !c8 && !(p.cit == 2 && p.cot == 2)) return SMSUT_EINVAL;     // (fused shortcut: 8-channel form or the tap-split kernel)
     if (p.cit == 1 && p.cot == 1) rc = launch_wgrad<3, 1, 1>(x, gy, workspace, N, H, W, Cin, Cout, p, 1, 1, st, x2, ca, aff, c8, c8 ? gs : nullptr);
     else if (p.cit == 1) rc = launch_wgrad<3, 1, 2>(x, gy, workspace, N, H, W, Cin, Cout, p, 1, 1, st, x2, ca, aff, c8, c8 ? gs : nullptr);
@@ -3337,15 +3283,13 @@ int smsut_conv2d_wgrad_mfma_slabs(const float* x, const float* gy, float* worksp
 //   gw10 [10][Cin][Cout]: rows 0..8 = sum_p x[p + tap] (x) gy[p]  (as smsut_conv2d_wgrad_mfma), row 9 = sum_p x[p] (x) gs[p].
 // xb nullable: non-null = x is the virtual cat([xa, xb]), ca channels in xa.  workspace: smsut_conv2d_wgrad_sc_ws floats.
 int smsut_conv2d_wgrad_sc_supported(int N, int H, int W, int Cin, int Cout) {
-  static const bool on = [] { const char* e = getenv("SMSUT_FUSE_SHORTCUT_WGRAD"); return !e || atoi(e) != 0; }();
   // the tap-split kernel's shapes (whole 32 x 32 channel slabs, full tiles): there the fusion wins 6-14 us per call.  On the
   // 16-channel slabs (32->16, 16->32) the extra tile pushed the row-split kernel over 256 VGPRs and the pair ran 0-7 us SLOWER
   // fused (scratch/wsc_ab.py) -- those keep the two-kernel form.
-  static const bool use_c8 = [] { const char* e = getenv("SMSUT_CONV_K8"); return !e || atoi(e) != 0; }();
-  if (on && use_c8 && Cin == 8 && Cout >= 4 && Cout % 4 == 0 && Cout <= 32 && N > 0 && H > 0 && W > 0) return 1;   // 8-channel form (SC8)
+  if (Cin == 8 && Cout >= 4 && Cout % 4 == 0 && Cout <= 32 && N > 0 && H > 0 && W > 0) return 1;   // 8-channel form (SC8)
   // register-row kernel (conv_wgrad_rr.hip): one more accumulator tile per (ci tile, co tile) -- also on the 16-channel slabs
-  if (on && smsut_wgrad_rr_eligible(N, H, W, Cin, Cout, nullptr, 0, false, true)) return 1;
-  return on && N > 0 && H > 0 && W > 0 && H % WTH == 0 && W % TW == 0 && Cin % 32 == 0 && Cout % 32 == 0 &&
+  if (smsut_wgrad_rr_eligible(N, H, W, Cin, Cout, nullptr, 0, false, true)) return 1;
+  return N > 0 && H > 0 && W > 0 && H % WTH == 0 && W % TW == 0 && Cin % 32 == 0 && Cout % 32 == 0 &&
          !plane_wgrad_applies(N, H, W, Cin, Cout) && (int64_t)N * H * W * (Cin > Cout ? Cin : Cout) < (1ll << 31);
 }
 int64_t smsut_conv2d_wgrad_sc_ws(int N, int H, int W, int Cin, int Cout) {
@@ -3375,8 +3319,7 @@ int smsut_conv2d_wgrad_mfma_cat(const float* xa, const float* xb, int ca, const 
 // rstd (x is the RAW conv output, lrelu(IN(.)) applied in flight: gamma, beta, slope shared -- same layer), gs (fused 1x1 shortcut,
 // gw holds 10 rows); each present in BOTH sets or in neither.
 int smsut_conv2d_wgrad_pair_supported(int NA, int NB, int H, int W, int Cin, int Cout, int cat, int aff, int sc) {
-  static const bool on = [] { const char* e = getenv("SMSUT_WGRAD_PAIR"); return !e || atoi(e) != 0; }();
-  if (!on || NA <= 0 || NB <= 0 || (cat && aff) || (aff && sc)) return 0;
+  if (NA <= 0 || NB <= 0 || (cat && aff) || (aff && sc)) return 0;
   if (sc && !smsut_conv2d_wgrad_sc_supported(NA + NB, H, W, Cin, Cout)) return 0;
   return smsut_wgrad_rr_eligible(NA + NB, H, W, Cin, Cout, cat ? (const float*)1 : nullptr, cat ? Cin / 2 : 0, aff != 0, sc != 0) ? 1 : 0;
 }
@@ -3579,10 +3522,9 @@ int smsut_conv2d_wgrad_f16_xh_inaff(const void* y1_16, const float* gy, float* g
   return SMSUT_OK;
 }
 // ... and the block's 1x1 shortcut weight gradient in the same pass: gw10 [10][Cin][Cout], rows 0..8 = the 3x3 taps, row 9 = the
-// shortcut's (as smsut_conv2d_wgrad_mfma_sc); gsc = smsut_absmax_scale2(gy, gs).  SMSUT_FUSE_SHORTCUT_WGRAD_F16=0 switches it off.
+// shortcut's (as smsut_conv2d_wgrad_mfma_sc); gsc = smsut_absmax_scale2(gy, gs).
 int smsut_conv2d_wgrad_sc_f16_supported(int N, int H, int W, int Cin, int Cout) {
-  static const bool on = [] { const char* e = getenv("SMSUT_FUSE_SHORTCUT_WGRAD_F16"); return !e || atoi(e) != 0; }();
-  return on && smsut_conv2d_wgrad_f16_supported(N, H, W, Cin, Cout);
+  return smsut_conv2d_wgrad_f16_supported(N, H, W, Cin, Cout);
 }
 int64_t smsut_conv2d_wgrad_sc_f16_ws(int N, int H, int W, int Cin, int Cout) {
   return (int64_t)plan_wgrad_f16(N, H, W, Cin, Cout).splits * 10 * Cin * Cout;

@@ -427,8 +427,7 @@ stem_wgrad(const float* __restrict__ x, const float* __restrict__ gy, float* __r
 }
 
 inline bool stem_shape(const SmallGeom& g) {
-  static const bool on = [] { const char* e = getenv("SMSUT_STEM"); return !e || atoi(e) != 0; }();
-  return on && g.KS == SKS && g.stride == 1 && g.pad == SPD && g.Cout == SCO && (g.Cin == 1 || g.Cin == 5) && g.H % STY == 0 &&
+  return g.KS == SKS && g.stride == 1 && g.pad == SPD && g.Cout == SCO && (g.Cin == 1 || g.Cin == 5) && g.H % STY == 0 &&
          g.W % STX == 0 && g.Ho == g.H && g.Wo == g.W;
 }
 inline int stem_wgrad_wgs(const SmallGeom& g, int max_slabs) {

@@ -358,32 +358,27 @@ __global__ void __launch_bounds__(TPB, (CIW == 2 && COW == 2) ? RR_OCC4 : 1) wgr
 
 // ---- plan ---------------------------------------------------------------------------------------------------------------------
 struct RrPlan {
-  int variant;            // 0 = not covered; 1: 16x16 per wave, 4 strips; 2: 32x16; 3: 16x32; 4: 32x32 per wave, 4 strips;
-                          // 5: 16x16 per wave, 2x2 sub-slabs, 1 strip; 6: 32x16 per wave, 1x2 sub-slabs, 2 strips
+  int variant;            // 0 = not covered; 1: 16x16 per wave, 4 strips; 2: 32x16; 3: 16x32; 4: 32x32 per wave, 4 strips
   int slab_ci, slab_co;   // channels per workgroup slab
   int ws;                 // strips per workgroup
   int R;                  // ring size = row-loop unroll
   int RC, groups_per_split, splits, total_wu;
 };
 
-int env_int(const char* name, int dflt) { const char* e = getenv(name); return e ? atoi(e) : dflt; }
+constexpr int RR_TARGET = 512;          // workgroups the split plan aims for: variants 1-3 ...
+constexpr int RR_TARGET4 = 256;         // ... and variant 4
+constexpr int RR_RCMAX = 64;            // longest row run of a work unit
 
 RrPlan plan_rr(int N, int H, int W, int Cin, int Cout, const float* x2, int ca, bool aff, bool sc) {
   RrPlan p{};
-  static const int on = env_int("SMSUT_WGRAD_RR", 1);
-  if (!on || N <= 0 || H < 4 || W < 16 || (W % 16) || (H % 4) || (Cin % 16) || (Cout % 16)) return p;
+  if (N <= 0 || H < 4 || W < 16 || (W % 16) || (H % 4) || (Cin % 16) || (Cout % 16)) return p;
   if ((int64_t)H * W * (Cin > Cout ? Cin : Cout) >= (1ll << 29)) return p;       // byte offsets inside an image are 32-bit
   if (x2 && (ca <= 0 || ca >= Cin || (ca % 16))) return p;
-  // variant for the 32 x 32 slabs: 4, 5 or 6 (tuning hook; anything else falls back to 4, so that eligible() never promises a
-  // plan launch() has no kernel for -- ADVICE r04)
-  static const int v32 = [] { const int v = env_int("SMSUT_RR_V32", 4); return (v == 4 || v == 5 || v == 6) ? v : 4; }();
   if (Cin == 16 && Cout == 16) { p.variant = 1; p.slab_ci = 16; p.slab_co = 16; p.ws = 4; }
   else if (Cin == 32 && Cout == 16) { p.variant = 2; p.slab_ci = 32; p.slab_co = 16; p.ws = 4; }
   else if (Cin == 16 && Cout == 32) { p.variant = 3; p.slab_ci = 16; p.slab_co = 32; p.ws = 4; }
-  else if (Cin % 32 == 0 && Cout % 32 == 0) {
-    const int v = v32;
-    p.variant = v; p.slab_ci = 32; p.slab_co = 32; p.ws = v == 4 ? 4 : (v == 5 ? 1 : 2);
-  } else return p;
+  else if (Cin % 32 == 0 && Cout % 32 == 0) { p.variant = 4; p.slab_ci = 32; p.slab_co = 32; p.ws = 4; }
+  else return p;
   if (aff && x2) return RrPlan{};
   p.R = (p.variant == 4 && !RR_V4R8) ? 4 : 8;
   if (H % p.R) {
@@ -391,13 +386,11 @@ RrPlan plan_rr(int N, int H, int W, int Cin, int Cout, const float* x2, int ca, 
     p.R = 4;
   }
   const int slabs = (Cin / p.slab_ci) * (Cout / p.slab_co);
-  static const int t_small = env_int("SMSUT_RR_TARGET", 512), t_big = env_int("SMSUT_RR_TARGET4", 256);
-  const int target = p.variant == 4 ? t_big : t_small;
+  const int target = p.variant == 4 ? RR_TARGET4 : RR_TARGET;
   int want = (target + slabs - 1) / slabs;
   if (want < 1) want = 1;
-  static const int rc_max = env_int("SMSUT_RR_RCMAX", 64);      // (64-row units where the grid still fills: B32 256^2 16->16 83 -> 78 us)
-  int rc = p.R;
-  for (int c = rc_max; c >= p.R; c >>= 1) {
+  int rc = p.R;                  // (64-row units where the grid still fills: B32 256^2 16->16 83 -> 78 us)
+  for (int c = RR_RCMAX; c >= p.R; c >>= 1) {
     if (c % p.R || H % c) continue;
     const int64_t groups = ((int64_t)N * (H / c) * (W / 16) + p.ws - 1) / p.ws;
     if (groups >= want || c == p.R) { rc = c; break; }
@@ -484,8 +477,6 @@ int smsut_wgrad_rr_launch(const float* x, const float* x2, int ca, const float* 
 #else
     case 4: return launch_v<2, 2, 1, 1, 4, 1>(a, p, st);
 #endif
-    case 5: return p.R == 8 ? launch_v<1, 1, 2, 2, 8, 3>(a, p, st) : launch_v<1, 1, 2, 2, 4, 1>(a, p, st);
-    case 6: return p.R == 8 ? launch_v<2, 1, 1, 2, 8, 3>(a, p, st) : launch_v<2, 1, 1, 2, 4, 1>(a, p, st);
   }
   return -1;
 }

@@ -868,10 +868,6 @@ restail_bwd_apply(const float* __restrict__ gout, const float* __restrict__ out,
   if constexpr (AMAX) { amax_emit(mx1, amax); amax_emit(mx2, amax + gridDim.x * gridDim.y); }
 }
 
-inline bool fin_emit_on() {                         // SMSUT_IN_ONE_CHUNK=0: always launch in_moments_final (A/B switch)
-  static const bool on = [] { const char* e = getenv("SMSUT_IN_ONE_CHUNK"); return !e || atoi(e) != 0; }();
-  return on;
-}
 inline int pick_chunk(int HW, int C, int N) {
   // aim for >= ~1024 blocks overall while keeping >= 256 pixels per chunk
 #ifndef SMSUT_IN_BLOCKS
@@ -887,13 +883,12 @@ inline int pick_chunk(int HW, int C, int N) {
 }
 
 // channel slabs for the partial-sum kernels: until ~512 workgroups, slabs of >= 16 channels (64 contiguous bytes per pixel)
+constexpr int IN_SLAB_WGS = 512;
 inline int slab_count(int N, int chunks, int C, int vec) {
-  static const bool on = [] { const char* e = getenv("SMSUT_IN_SLABS"); return !e || atoi(e) != 0; }();
-  if (!on || vec != 4) return 1;
+  if (vec != 4) return 1;
   const int cv = C / 4;
   int z = 1;
-  static const int target = [] { const char* e = getenv("SMSUT_IN_SLAB_WGS"); return e ? atoi(e) : 512; }();
-  while ((int64_t)N * chunks * z < target && cv % (2 * z) == 0 && cv / (2 * z) >= 4) z *= 2;
+  while ((int64_t)N * chunks * z < IN_SLAB_WGS && cv % (2 * z) == 0 && cv / (2 * z) >= 4) z *= 2;
   return z;
 }
 
@@ -911,7 +906,7 @@ int smsut_instnorm_fwd(const float* x, const float* gamma, const float* beta, fl
   const int ppc = pick_chunk(HW, C, N);
   const int chunks = (int)cdiv64(HW, ppc);
   dim3 g(chunks, N, slab_count(N, chunks, C, C % 4 == 0 ? 4 : 1));
-  const FinOut fin = (chunks == 1 && fin_emit_on()) ? FinOut{mean, rstd, nullptr, eps} : FinOut{};
+  const FinOut fin = chunks == 1 ? FinOut{mean, rstd, nullptr, eps} : FinOut{};
   if (C % 4 == 0)
     in_moments_partial<0, 4><<<g, TPB, 0, st>>>(x, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, workspace, HW, C, ppc, slope, fin);
   else
@@ -980,7 +975,7 @@ int smsut_instnorm_bwd(const float* gy, const float* x, const float* beta, const
   const int ppc = pick_chunk(HW, C, N);
   const int chunks = (int)cdiv64(HW, ppc);
   dim3 g(chunks, N, slab_count(N, chunks, C, C % 4 == 0 ? 4 : 1));
-  const FinOut fin = (chunks == 1 && fin_emit_on()) ? FinOut{a_mean, b_mean, nullptr, 0.f} : FinOut{};
+  const FinOut fin = chunks == 1 ? FinOut{a_mean, b_mean, nullptr, 0.f} : FinOut{};
   if (C % 4 == 0)
     in_moments_partial<1, 4><<<g, TPB, 0, st>>>(gy, x, nullptr, gamma, beta, mean, rstd, workspace, HW, C, ppc, slope, fin);
   else
@@ -1028,7 +1023,7 @@ int smsut_instnorm_pool_bwd(const float* gyp, const float* x, const float* beta,
   const int ppc = pick_chunk(HW, C, N);
   const int chunks = (int)cdiv64(HW, ppc);
   dim3 g(chunks, N, slab_count(N, chunks, C, C % 4 == 0 ? 4 : 1));
-  const FinOut fin = (chunks == 1 && fin_emit_on()) ? FinOut{a_mean, b_mean, nullptr, 0.f} : FinOut{};
+  const FinOut fin = chunks == 1 ? FinOut{a_mean, b_mean, nullptr, 0.f} : FinOut{};
   if (C % 4 == 0)
     in_moments_partial<1, 4, true><<<g, TPB, 0, st>>>(gyp, x, nullptr, gamma, beta, mean, rstd, workspace, HW, C, ppc, slope, fin, W);
   else
@@ -1059,7 +1054,7 @@ int smsut_instnorm_bwd2(const float* v, const float* ug, const float* ub, const 
   const int chunks = (int)cdiv64(HW, ppc);
   dim3 g(chunks, N, slab_count(N, chunks, C, C % 4 == 0 ? 4 : 1));
   float* cvm = scratch; float* dvm = scratch + (size_t)N * C; float* em = scratch + 2 * (size_t)N * C;
-  const FinOut fin = (chunks == 1 && fin_emit_on()) ? FinOut{cvm, dvm, em, 0.f} : FinOut{};
+  const FinOut fin = chunks == 1 ? FinOut{cvm, dvm, em, 0.f} : FinOut{};
   if (C % 4 == 0)
     in_moments_partial<2, 4><<<g, TPB, 0, st>>>(v, x, gy, gamma, beta, mean, rstd, workspace, HW, C, ppc, slope, fin);
   else
@@ -1202,7 +1197,7 @@ static int restail_bwd_launch(const float* gout, const float* out, const float* 
   const int chunks = (int)cdiv64(HW, ppc);
   dim3 g(chunks, N, slab_count(N, chunks, C, C % 4 == 0 ? 4 : 1));
   const bool remask = ms && b2 && bs;
-  const FinOut fin = (chunks == 1 && fin_emit_on()) ? FinOut{a_mean, b2_mean, bs_mean, 0.f} : FinOut{};
+  const FinOut fin = chunks == 1 ? FinOut{a_mean, b2_mean, bs_mean, 0.f} : FinOut{};
 #define TAIL_PARTIAL(V, R) restail_bwd_partial<V, R><<<g, TPB, 0, st>>>(gout, out, t, workspace, HW, C, ppc, slope, fin)
   // in-launch finalize (several chunks per image, fp32, the two-IN tail on whole float4 channel groups): the last-arriving
   // workgroup of an image combines its partials -- no in_moments_final<2> launch

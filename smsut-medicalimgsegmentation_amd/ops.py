@@ -26,8 +26,6 @@ from . import _hip as H
 IN_EPS = 1e-5
 
 import os as _os
-# debugging / cross-check switch: route every conv through the shape-complete direct kernels
-FORCE_GENERIC_CONV = bool(int(_os.environ.get("SMSUT_FORCE_GENERIC_CONV", "0")))
 
 _INPUT_GRADS_ONLY = False
 
@@ -180,8 +178,7 @@ def conv_dtype() -> str:
 # passed with the call): then it copies the image by LDS-DMA.  An image is only right while the weights it was made from are
 # unchanged, so images are made on entry of a scope in which the caller guarantees exactly that (a trainer's forward / backward
 # phase: weights change in optimizer.step(), between phases) and forgotten when it closes; a module called
-# outside such a scope runs the on-the-fly form.  Results are bit-identical either way.  ``SMSUT_WINO_PREPARED=0`` turns the scopes into no-ops.
-WINO_PREPARED = _os.environ.get("SMSUT_WINO_PREPARED", "1") not in ("0", "")
+# outside such a scope runs the on-the-fly form.  Results are bit-identical either way.
 _WINO_MIN_K = 64
 # Images in force: (weight data_ptr, form 0 forward / 1 data-gradient) -> device address.  HOST-side state of this wrapper, filled
 # and emptied by the ``wino_prepared`` scopes; the C-ABI library keeps none (r03's smsut_wino_bind* registry is gone): the image
@@ -287,7 +284,7 @@ def wino_prepared(*modules: torch.nn.Module, forms: str = "fb"):
     launch per module and form -- inside a hipGraph capture it becomes part of the captured phase, which therefore never
     depends on what another phase left behind) and bound for the convolutions inside; unbound on exit."""
     active = []
-    if WINO_PREPARED and not CONV_F16:
+    if not CONV_F16:
         for m in modules:
             ws = m.__dict__.get("_smsut_wino_set")
             if ws is None or ws.stale_layout(m):
@@ -349,7 +346,7 @@ def _conv_fwd_launch(x, w, bias, stride, pad, want_stats=False, f16=False):
     assert ci == ci2, f"conv: Cin mismatch {ci} vs {ci2}"
     ho, wo = _out_size(h, kh, stride, pad), _out_size(wd, kw, stride, pad)
     y = new_act(n, co, ho, wo, x)
-    if kh == 1 and kw == 1 and stride == 1 and pad == 0 and not FORCE_GENERIC_CONV and H.call("smsut_conv1x1_supported", ci, co):
+    if kh == 1 and kw == 1 and stride == 1 and pad == 0 and H.call("smsut_conv1x1_supported", ci, co):
         tiles = H.call("smsut_conv1x1_tiles", n, h * wd, co) if (want_stats and bias is None) else 0
         part = _ws(n * tiles * co * 2, x) if tiles else None
         H.call("smsut_conv1x1_fwd", x, w, y, part, n, h * wd, ci, co, 0, _s())
@@ -358,7 +355,7 @@ def _conv_fwd_launch(x, w, bias, stride, pad, want_stats=False, f16=False):
         if tiles:
             y._smsut_in_partials = (part, tiles)
         return y
-    if kh == kw and not FORCE_GENERIC_CONV and H.call("smsut_conv2d_mfma_supported", kh, stride, pad, ci, co):
+    if kh == kw and H.call("smsut_conv2d_mfma_supported", kh, stride, pad, ci, co):
         f16 = f16 and bool(H.call("smsut_conv2d_f16_supported", kh, ci, co))
         if want_stats and bias is None:
             # fused InstanceNorm statistics: the conv epilogue leaves {sum, sum^2} partials that the following
@@ -375,13 +372,13 @@ def _conv_fwd_launch(x, w, bias, stride, pad, want_stats=False, f16=False):
             _conv3("smsut_conv2d_fwd_mfma", w, 0, x, w, y, n, h, wd, ci, co, kh, 0, _s())
         if bias is not None:
             H.call("smsut_bias_add", y, bias, y, n * ho * wo, co, _s())
-    elif (kh == 4 and kw == 4 and stride == 1 and pad == 1 and not FORCE_GENERIC_CONV
+    elif (kh == 4 and kw == 4 and stride == 1 and pad == 1
           and H.call("smsut_conv2d_k4_supported", ci, co)):
         # networks.NLayerDiscriminator (networks.py:977-1032): 4x4 s1 p1 on the matrix cores
         H.call("smsut_conv2d_k4_fwd", x, w, y, n, h, wd, ci, co, 0, _s())
         if bias is not None:
             H.call("smsut_bias_add", y, bias, y, n * ho * wo, co, _s())
-    elif kh == kw and not FORCE_GENERIC_CONV and H.call("smsut_conv2d_small_supported", kh, ci, co):
+    elif kh == kw and H.call("smsut_conv2d_small_supported", kh, ci, co):
         H.call("smsut_conv2d_small_fwd", x, w, bias, y, n, h, wd, ci, ho, wo, co, kh, stride, pad, _s())
     else:
         H.call("smsut_conv2d_fwd_generic", x, w, bias, y, n, h, wd, ci, ho, wo, co, kh, kw, stride, pad, _s())
@@ -393,22 +390,22 @@ def _conv_dgrad_launch(gy, w, h, wd, stride, pad, f16=False):
     co2, ci, kh, kw = w.shape
     assert co == co2
     gx = new_act(n, ci, h, wd, gy)
-    one_by_one = kh == 1 and kw == 1 and stride == 1 and pad == 0 and not FORCE_GENERIC_CONV
-    if one_by_one and THIN_1X1 and co % 4 != 0 and H.call("smsut_conv1x1_thin_supported", ci, co):   # heads: 1, 5 channels
+    one_by_one = kh == 1 and kw == 1 and stride == 1 and pad == 0
+    if one_by_one and co % 4 != 0 and H.call("smsut_conv1x1_thin_supported", ci, co):   # heads: 1, 5 channels
         H.call("smsut_conv1x1_thin_dgrad", gy, w, gx, n, h * wd, ci, co, _s())
         return gx
-    if kh == 1 and kw == 1 and stride == 1 and pad == 0 and not FORCE_GENERIC_CONV and H.call("smsut_conv1x1_supported", co, ci):
+    if kh == 1 and kw == 1 and stride == 1 and pad == 0 and H.call("smsut_conv1x1_supported", co, ci):
         H.call("smsut_conv1x1_fwd", gy, w, gx, None, n, h * wd, co, ci, 1, _s())
         return gx
-    if kh == kw and not FORCE_GENERIC_CONV and H.call("smsut_conv2d_mfma_supported", kh, stride, pad, co, ci):
+    if kh == kw and H.call("smsut_conv2d_mfma_supported", kh, stride, pad, co, ci):
         if f16 and H.call("smsut_conv2d_f16_supported", kh, co, ci):
             H.call("smsut_conv2d_fwd_mfma_f16", gy, w, gx, _grad_scale(gy), n, h, wd, co, ci, kh, 1, _s())
         else:
             _conv3("smsut_conv2d_fwd_mfma", w, 1, gy, w, gx, n, h, wd, co, ci, kh, 1, _s())
-    elif (kh == 4 and kw == 4 and stride == 1 and pad == 1 and not FORCE_GENERIC_CONV
+    elif (kh == 4 and kw == 4 and stride == 1 and pad == 1
           and H.call("smsut_conv2d_k4_supported", ci, co)):
         H.call("smsut_conv2d_k4_fwd", gy, w, gx, n, h, wd, ci, co, 1, _s())
-    elif kh == kw and not FORCE_GENERIC_CONV and H.call("smsut_conv2d_small_supported", kh, ci, co):
+    elif kh == kw and H.call("smsut_conv2d_small_supported", kh, ci, co):
         H.call("smsut_conv2d_small_dgrad", gy, w, gx, n, h, wd, ci, ho, wo, co, kh, stride, pad, _s())
     else:
         H.call("smsut_conv2d_dgrad_generic", gy, w, gx, n, h, wd, ci, ho, wo, co, kh, kw, stride, pad, _s())
@@ -419,26 +416,26 @@ def _conv_wgrad_launch(x, gy, kh, kw, stride, pad, f16=False):
     n, ci, h, wd = x.shape
     _, co, ho, wo = gy.shape
     gw = new_weight(co, ci, kh, kw, device=x.device)
-    one_by_one = kh == 1 and kw == 1 and stride == 1 and pad == 0 and not FORCE_GENERIC_CONV
-    if one_by_one and THIN_1X1 and co % 4 != 0 and H.call("smsut_conv1x1_thin_supported", ci, co):
+    one_by_one = kh == 1 and kw == 1 and stride == 1 and pad == 0
+    if one_by_one and co % 4 != 0 and H.call("smsut_conv1x1_thin_supported", ci, co):
         H.call("smsut_conv1x1_thin_wgrad", x, gy, gw, _ws(H.call("smsut_conv1x1_thin_wgrad_ws", ci), x), n, h * wd, ci, co, _s())
         return gw
-    if kh == 1 and kw == 1 and stride == 1 and pad == 0 and not FORCE_GENERIC_CONV and ci % 4 == 0 and co % 4 == 0:
+    if kh == 1 and kw == 1 and stride == 1 and pad == 0 and ci % 4 == 0 and co % 4 == 0:
         H.call("smsut_conv1x1_wgrad", x, gy, gw, _ws(H.call("smsut_conv1x1_wgrad_ws", n, h * wd, ci, co), x), n, h * wd, ci, co, _s())
         return gw
-    if (f16 and kh == 3 and kw == 3 and stride == 1 and pad == 1 and not FORCE_GENERIC_CONV
+    if (f16 and kh == 3 and kw == 3 and stride == 1 and pad == 1
             and H.call("smsut_conv2d_wgrad_f16_supported", n, h, wd, ci, co)):
         ws = _ws(H.call("smsut_conv2d_wgrad_f16_ws", n, h, wd, ci, co), x)
         H.call("smsut_conv2d_wgrad_f16", x, None, 0, gy, gw, ws, _grad_scale(gy), n, h, wd, ci, co, _s())
         return gw
-    if kh == kw and not FORCE_GENERIC_CONV and H.call("smsut_conv2d_wgrad_mfma_supported", kh, stride, pad, ci, co):
+    if kh == kw and H.call("smsut_conv2d_wgrad_mfma_supported", kh, stride, pad, ci, co):
         ws = _ws(H.call("smsut_conv2d_wgrad_mfma_ws", n, h, wd, ci, co, kh), x)
         H.call("smsut_conv2d_wgrad_mfma", x, gy, gw, ws, n, h, wd, ci, co, kh, _s())
-    elif (kh == 4 and kw == 4 and stride == 1 and pad == 1 and not FORCE_GENERIC_CONV
+    elif (kh == 4 and kw == 4 and stride == 1 and pad == 1
           and H.call("smsut_conv2d_k4_supported", ci, co)):
         ws = _ws(H.call("smsut_conv2d_k4_wgrad_ws", n, h, wd, ci, co), x)
         H.call("smsut_conv2d_k4_wgrad", x, gy, gw, ws, n, h, wd, ci, co, _s())
-    elif kh == kw and not FORCE_GENERIC_CONV and H.call("smsut_conv2d_flat_wgrad_supported", kh, stride, ci, co):
+    elif kh == kw and H.call("smsut_conv2d_flat_wgrad_supported", kh, stride, ci, co):
         ws = _ws(H.call("smsut_conv2d_flat_wgrad_ws", n, ho, wo, ci, co, kh), x)
         H.call("smsut_conv2d_flat_wgrad", x, gy, gw, ws, n, h, wd, ci, ho, wo, co, kh, stride, pad, _s())
     else:
@@ -813,8 +810,6 @@ class ResTailFn(Function):
             H.call("smsut_avgpool2_bwd", nhwc(g_pooled), g_out, n, h, w, c, _s())
             g_pooled = None
         mp = ctx.pool and g_pooled is not None
-        if not REMASK_TAIL and not mp:
-            b2 = bs = None
         g_out = nhwc(g_out)
         hw = h * w
         dev = y2.device
@@ -847,7 +842,7 @@ TAIL_AVGPOOL = bool(int(_os.environ.get("SMSUT_TAIL_AVGPOOL", "1")))     # Bottl
 
 
 def res_tail_pool_fusable(y2):
-    return TAIL_AVGPOOL and REMASK_TAIL and y2.shape[1] % 4 == 0 and y2.shape[2] % 2 == 0 and y2.shape[3] % 2 == 0
+    return TAIL_AVGPOOL and y2.shape[1] % 4 == 0 and y2.shape[2] % 2 == 0 and y2.shape[3] % 2 == 0
 
 
 def res_tail_pool(y2, g2, b2, s, gs, bs, slope):
@@ -857,27 +852,16 @@ def res_tail_pool(y2, g2, b2, s, gs, bs, slope):
 
 # ------------------------------------------------------------------------------------------- fused BasicBlock
 FUSED_BLOCK = bool(int(_os.environ.get("SMSUT_FUSED_BLOCK", "1")))
-ONE_PASS_CONCAT = bool(int(_os.environ.get("SMSUT_ONE_PASS_CONCAT", "1")))     # cat / split as one kernel over full rows
 FUSED_RES_TAIL = bool(int(_os.environ.get("SMSUT_FUSED_RES_TAIL", "1")))       # BottleBlock tail in first_order_pass()
-INAFF_CONV2 = bool(int(_os.environ.get("SMSUT_INAFF_CONV2", "1")))   # conv2 / wgrad2 of a fused block normalise y1 while staging
-# ... for blocks of whole 16-channel tiles (r04: the register-row weight gradient takes the transform for +3 us at 16 -> 16 @256^2;
-# the LDS-staged 16-channel kernel paid +55 us, which kept the 16-channel blocks out until then: uganConsis -1.0 %, U-Net -1.0 %)
-INAFF_MIN_CO = int(_os.environ.get("SMSUT_INAFF_MIN_CO", "16"))
-POOL_SKIP = bool(int(_os.environ.get("SMSUT_POOL_SKIP", "1")))       # encoder level: skip gradient summed inside the pooling backward
 VIRTUAL_CAT = bool(int(_os.environ.get("SMSUT_VIRTUAL_CAT", "1")))   # block-after-concat reads [up, skip] in place (no cat tensor)
 SPLIT_DGRAD = bool(int(_os.environ.get("SMSUT_SPLIT_DGRAD", "1")))   # block-after-concat: gradient written into the two parts
-THIN_1X1 = bool(int(_os.environ.get("SMSUT_THIN_1X1", "1")))         # streaming dgrad / wgrad of the <= 8-channel 1x1 heads
-REMASK_TAIL = bool(int(_os.environ.get("SMSUT_REMASK_TAIL", "1")))   # two-IN tail backward: mask from y2, s instead of reading out
-FUSED_BWD_STATS = bool(int(_os.environ.get("SMSUT_FUSED_BWD_STATS", "1")))     # IN-backward statistics in the dgrad epilogue
-HS_INAFF = bool(int(_os.environ.get("SMSUT_HS_INAFF", "1")))              # half storage: conv2 / its weight gradient normalise y1 while staging
-F16_STORE = bool(int(_os.environ.get("SMSUT_F16_STORE", "1")))           # fp16 operands: block-internal y1 / y2 / s stored as fp16
 AMAX_HANDOVER = bool(int(_os.environ.get("SMSUT_AMAX_HANDOVER", "1")))    # fp16 operands: gradient maxima from the producing kernels
 
 
 def basic_block_fusable(x, w1, ws):
     """The fused path needs the MFMA kernels on every conv of the block: channel counts that are multiples of 4."""
     co, ci = w1.shape[0], w1.shape[1]
-    return (FUSED_BLOCK and not FORCE_GENERIC_CONV and x.is_cuda and ci % 4 == 0 and co % 4 == 0 and ci >= 4 and co >= 4
+    return (FUSED_BLOCK and x.is_cuda and ci % 4 == 0 and co % 4 == 0 and ci >= 4 and co >= 4
             and (ws is not None or ci == co))
 
 
@@ -892,11 +876,9 @@ def basic_block_fusable(x, w1, ws):
 #   * inside a GraphedPhase capture: slices of a per-capture chunk allocated (and zero-filled: one fill node, replayed first) in
 #     that graph's own pool -- a replay re-zeroes its tickets before use, and no eager launch ever shares them;
 #   * inside somebody else's stream capture: no in-launch finalize (the separate launch runs).
-# ``SMSUT_FIN=0`` switches the whole thing off (A/B).
+# It is carried by conv1 + shortcut and conv2 (forward; the two go together: conv2 reads what conv1's launch finalised), conv2's
+# data-gradient and the residual tail's backward.  ``SMSUT_FIN=0`` switches the whole thing off (A/B).
 FIN_ON = bool(int(_os.environ.get("SMSUT_FIN", "1")))
-# which launches carry it (A/B hook): 1 = conv1 + shortcut and conv2 (forward; the two go together: conv2 reads what conv1's launch
-# finalised), 4 = conv2's data-gradient, 8 = the residual tail's backward
-FIN_MASK = int(_os.environ.get("SMSUT_FIN_MASK", "13"))
 _TICKET_RING = {}            # device index -> [tensor, position]
 _TICKET_CHUNKS = {}          # (device index, capture seq) -> [tensor, position]: the chunk being filled
 _TICKET_KEEP = []            # every chunk ever made, for the life of the process (32 KB each)
@@ -945,7 +927,7 @@ def _wu(w, transposed):
 # (``_PAIR_STASH``, keyed by the weight's storage -- the cycle pass runs on parameter aliases of the same storage) and returns no
 # weight gradient; the node of the other pass launches ONE ``smsut_conv2d_wgrad_pair`` over both image sets and returns the sum.
 # Same products, summed in the kernel's accumulators instead of by a separate add; deterministic (autograd's order is).
-# ``SMSUT_WGRAD_PAIR=0`` (read by the library: ``smsut_conv2d_wgrad_pair_supported`` then says no) keeps two launches.
+# Where ``smsut_conv2d_wgrad_pair_supported`` says no, the two passes keep two launches.
 _PAIR_FWD = False
 _PAIR_STASH = {}
 
@@ -1081,17 +1063,16 @@ class BasicBlockFn(Function):
         # fp16 operands: the block-internal raw conv outputs y1, y2, s never leave the block -- stored as fp16 (half the HBM bytes
         # of every pass over them: conv epilogues, IN apply, both tail passes, the BST mask read), arithmetic on them in fp32
         # (the 8 -> 16 first block: conv1 stays on fp32 operands -- the 8-channel form has no fp16 twin -- and stores fp16 all the same)
-        hs = (F16_STORE and (f16a or ci == 8) and f16 and fused_sc and FUSED_BWD_STATS and REMASK_TAIL
+        hs = ((f16a or ci == 8) and f16 and fused_sc
               and bool(H.call("smsut_conv2d_f16_hs_supported", n, h, w, ci, co, 1 if virtual else 0))
               and bool(H.call("smsut_conv2d_f16_hs_supported", n, h, w, co, co, 0)))
         ctx.hs = hs
         act_dt = torch.float16 if hs else torch.float32
         # in-launch finalize of all three statistics sets of the block (fp32, fused shortcut, conv2 on the raw y1: the forms whose
         # kernels carry it) -- decided once, so that the block never mixes the two ways for one statistics set
-        fin = (fused_sc and not (f16a or f16 or hs) and INAFF_CONV2 and co % INAFF_MIN_CO == 0
+        fin = (fused_sc and not (f16a or f16 or hs) and co % 16 == 0
                and bool(H.call("smsut_conv2d_mfma_persistent", n, h, w, co, co, 3, 0)) and _tickets(0, x) is not None)
         ctx.fin = fin
-        fin = fin and bool(FIN_MASK & 1)
         y1 = new_act(n, co, h, w, x, act_dt)
         if fused_sc:
             s = new_act(n, co, h, w, x, act_dt)
@@ -1117,7 +1098,10 @@ class BasicBlockFn(Function):
             m1, r1 = stat(co)
         y2 = new_act(n, co, h, w, x, act_dt)
         p2 = _ws(n * t3b * co * 2, x)
-        inaff = (INAFF_CONV2 and not f16 and co % INAFF_MIN_CO == 0
+        # conv2 / wgrad2 normalise y1 while staging, for blocks of whole 16-channel tiles (r04: the register-row weight gradient takes
+        # the transform for +3 us at 16 -> 16 @256^2; the LDS-staged 16-channel kernel paid +55 us, which kept the 16-channel blocks
+        # out until then: uganConsis -1.0 %, U-Net -1.0 %)
+        inaff = (not f16 and co % 16 == 0
                  and bool(H.call("smsut_conv2d_mfma_persistent", n, h, w, co, co, 3, 0)))
         ctx.inaff = inaff
         if inaff and fin:
@@ -1131,17 +1115,12 @@ class BasicBlockFn(Function):
             H.call("smsut_in_finalize_fwd", p1, t3, m1, r1, n, hw, co, IN_EPS, st)
             _conv3("smsut_conv2d_fwd_mfma_stats_inaff", w2, 0, y1, w2, y2, p2, m1, r1, g1, b1, slope, n, h, w, co, co, st)
         else:
-            if hs and HS_INAFF:
+            if hs:
                 # conv2 (and later its weight gradient) widen the raw fp16 y1, normalise + activate and round it while staging: the
                 # operand bits smsut_instnorm_fwd_partials_hs2 would have stored -- a1 and the pass that writes it disappear
                 a1 = None
                 H.call("smsut_in_finalize_fwd", p1, t3, m1, r1, n, hw, co, IN_EPS, st)
                 H.call("smsut_conv2d_fwd_mfma_stats_inaff_f16_hsx", y1, w2, y2, p2, m1, r1, g1, b1, slope, n, h, w, co, co, st)
-            elif hs:
-                # (a1 as fp16 changes nothing downstream: conv2 and its weight gradient round their x operand to fp16 anyway)
-                a1 = new_act(n, co, h, w, x, act_dt)
-                H.call("smsut_instnorm_fwd_partials_hs2", y1, g1, b1, a1, m1, r1, p1, t3, n, hw, co, IN_EPS, slope, 1, st)
-                H.call("smsut_conv2d_fwd_mfma_stats_f16_hsx", a1, w2, y2, p2, n, h, w, co, co, st)
             else:
                 a1 = new_act(n, co, h, w, x)
                 H.call("smsut_instnorm_fwd_partials", y1, g1, b1, a1, m1, r1, p1, t3, n, hw, co, IN_EPS, slope, 1, st)
@@ -1200,12 +1179,8 @@ class BasicBlockFn(Function):
         xb_part = None
         if ctx.virtual:
             x, w1, w2, ws, y1, a1, y2, s, out, m1, r1, m2, r2, ms, rs, g1, b1, g2, gs, b2, bs, xb_part = ctx.saved_tensors
-            if not REMASK_TAIL:
-                b2 = bs = None
         elif ctx.has_sc:
             x, w1, w2, ws, y1, a1, y2, s, out, m1, r1, m2, r2, ms, rs, g1, b1, g2, gs, b2, bs = ctx.saved_tensors
-            if not REMASK_TAIL:
-                b2 = bs = None
         else:
             x, w1, w2, y1, a1, y2, out, m1, r1, m2, r2, g1, b1, g2 = ctx.saved_tensors
             ws = ms = rs = gs = b2 = bs = None
@@ -1243,7 +1218,7 @@ class BasicBlockFn(Function):
         amax = torch.empty(3 * nb, dtype=torch.float32, device=dev) if nb else None
         hs = ctx.hs
         if mp:
-            tk = _tickets(n, x) if (not hs and amax is None and bool(FIN_MASK & 8) and _tickets(0, x) is not None) else None
+            tk = _tickets(n, x) if (not hs and amax is None and _tickets(0, x) is not None) else None
             H.call("smsut_restail_bwd_pool", g_out, g_pooled, ctx.pool_idx, y2, m2, r2, g2, b2, s, ms, rs, gs, bs, gy2, gs_t, a_t, b2_t,
                    bs_t, gg2, gb2, ggs, gbs, _ws(n * chunks * co * 3, x), tk, amax, n, h, w, co, slope, int(hs), st)
         elif hs:
@@ -1252,7 +1227,7 @@ class BasicBlockFn(Function):
         elif amax is not None:
             H.call("smsut_restail_bwd_amax", g_out, out, y2, m2, r2, g2, b2, s, ms, rs, gs, bs, gy2, gs_t, a_t, b2_t, bs_t, gg2, gb2,
                    ggs, gbs, _ws(n * chunks * co * 3, x), amax, n, hw, co, slope, st)
-        elif ctx.has_sc and bool(FIN_MASK & 8) and _tickets(0, x) is not None:
+        elif ctx.has_sc and _tickets(0, x) is not None:
             # the per-image means of the tail's backward finalised inside the partial-sum launch (two launches instead of three)
             H.call("smsut_restail_bwd_fin", g_out, out, y2, m2, r2, g2, b2, s, ms, rs, gs, bs, gy2, gs_t, a_t, b2_t, bs_t, gg2, gb2,
                    ggs, gbs, _ws(n * chunks * co * 3, x), _tickets(n, x), n, hw, co, slope, st)
@@ -1267,11 +1242,11 @@ class BasicBlockFn(Function):
         a1m, b1m, gg1, gb1 = vec(n, co), vec(n, co), vec(co), vec(co)
         sc2 = (_grad_scale_from(amax[:nb]) if amax is not None else _grad_scale(gy2)) if f16 else None   # serves conv2's data- and weight-gradient
         amax1 = False                                        # amax[2] = max |gy1| written
-        if FUSED_BWD_STATS and H.call("smsut_conv2d_mfma_persistent", n, h, w, co, co, 3, int(f16)):
+        if H.call("smsut_conv2d_mfma_persistent", n, h, w, co, co, 3, int(f16)):
             # the dgrad epilogue masks its result and emits the InstanceNorm-backward partial sums: no reduction pass
             tb = H.call("smsut_conv2d_mfma_tiles", n, h, w, co, co, 3, int(f16))
             pb = _ws(n * tb * co * 2, x)
-            fin_b = ctx.fin and bool(FIN_MASK & 4) and not (hs or f16) and _tickets(0, x) is not None      # in-launch finalize of the backward pair
+            fin_b = ctx.fin and not (hs or f16) and _tickets(0, x) is not None      # in-launch finalize of the backward pair
             if hs:
                 H.call("smsut_conv2d_dgrad_mfma_bwdstats_f16_hs", gy2, w2, ga1, pb, y1, m1, r1, g1, b1, sc2, slope, n, h, w, co, co, st)
             elif f16:
@@ -1302,12 +1277,9 @@ class BasicBlockFn(Function):
         f16w2 = f16 and bool(H.call("smsut_conv2d_wgrad_f16_supported", n, h, w, co, co))
         f16w1 = f16a and bool(H.call("smsut_conv2d_wgrad_f16_supported", n, h, w, ci, co))
         gw2 = new_weight(co, co, 3, 3, device=dev) if (hs or f16w2) else None
-        if hs and a1 is None:
+        if hs:
             H.call("smsut_conv2d_wgrad_f16_xh_inaff", y1, gy2, gw2, _ws(H.call("smsut_conv2d_wgrad_f16_ws", n, h, w, co, co), x), sc2,
                    m1, r1, g1, b1, slope, n, h, w, co, co, st)
-        elif hs:
-            H.call("smsut_conv2d_wgrad_f16_xh", a1, gy2, gw2, _ws(H.call("smsut_conv2d_wgrad_f16_ws", n, h, w, co, co), x), sc2,
-                   n, h, w, co, co, st)
         elif f16w2:
             H.call("smsut_conv2d_wgrad_f16", a1, None, 0, gy2, gw2, _ws(H.call("smsut_conv2d_wgrad_f16_ws", n, h, w, co, co), x),
                    sc2, n, h, w, co, co, st)
@@ -1477,7 +1449,7 @@ class CatParts:
 def concat_channels_deferred(a, b):
     """cat([a, b], 1) whose materialisation is left to the consumer (see CatParts); a plain tensor when the virtual-cat
     kernels cannot apply (unequal or non-16-multiple halves, CPU tensors, switches off)."""
-    if (VIRTUAL_CAT and SPLIT_DGRAD and FUSED_BLOCK and not FORCE_GENERIC_CONV and a.is_cuda and a.shape[1] == b.shape[1]
+    if (VIRTUAL_CAT and SPLIT_DGRAD and FUSED_BLOCK and a.is_cuda and a.shape[1] == b.shape[1]
             and a.shape[1] % 16 == 0 and a.shape[0] == b.shape[0] and a.shape[2:] == b.shape[2:]):
         return CatParts(a, b)
     return concat_channels(a, b)
@@ -1504,7 +1476,7 @@ BLOCK_POOL = bool(int(_os.environ.get("SMSUT_BLOCK_POOL", "1")))     # encoder l
 def basic_block_pool_fusable(x, w1, ws):
     """The fused block applies, it has a conv shortcut (two-IN tail), whole channel quads, an even plane -- and a gradient is wanted
     (the inference path keeps block + pooling)."""
-    return (BLOCK_POOL and POOL_SKIP and ws is not None and REMASK_TAIL and basic_block_fusable(x, w1, ws) and w1.shape[0] % 4 == 0
+    return (BLOCK_POOL and ws is not None and basic_block_fusable(x, w1, ws) and w1.shape[0] % 4 == 0
             and x.shape[2] % 2 == 0 and x.shape[3] % 2 == 0 and torch.is_grad_enabled() and (x.requires_grad or w1.requires_grad)
             and getattr(x, "_smsut_cat_parts", None) is None)
 
@@ -1650,8 +1622,8 @@ class MaxPool2SkipFn(Function):
 
 
 def max_pool2_skip(x):
-    """(pooled, skip) of an encoder level; plain (max_pool2(x), x) when the fused form is switched off."""
-    if POOL_SKIP and x.is_cuda and x.requires_grad and torch.is_grad_enabled():
+    """(pooled, skip) of an encoder level; plain (max_pool2(x), x) off the GPU or when no gradient is wanted."""
+    if x.is_cuda and x.requires_grad and torch.is_grad_enabled():
         return MaxPool2SkipFn.apply(x)
     return max_pool2(x), x
 
@@ -1787,7 +1759,7 @@ class ConcatFn(Function):
         assert b.shape[0] == n and b.shape[2:] == a.shape[2:]
         y = new_act(n, ca + cb, h, w, a)
         p = n * h * w
-        if ONE_PASS_CONCAT and ca % 4 == 0 and cb % 4 == 0:
+        if ca % 4 == 0 and cb % 4 == 0:
             H.call("smsut_concat2", a, ca, b, cb, y, p, 0, _s())
         else:
             H.call("smsut_copy_channels", a, ca, 0, y, ca + cb, 0, ca, p, _s())
@@ -1804,7 +1776,7 @@ class ConcatFn(Function):
         p = n * h * w
         ga = new_act(n, ca, h, w, gy) if ctx.needs_input_grad[0] else None
         gb = new_act(n, cb, h, w, gy) if ctx.needs_input_grad[1] else None
-        if ONE_PASS_CONCAT and ca % 4 == 0 and cb % 4 == 0 and (ga is not None or gb is not None):
+        if ca % 4 == 0 and cb % 4 == 0 and (ga is not None or gb is not None):
             H.call("smsut_concat2", ga, ca, gb, cb, gy, p, 1, _s())
         else:
             if ga is not None:

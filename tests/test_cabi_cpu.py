@@ -72,7 +72,7 @@ def test_support_queries_and_workspace_sizes(built):
     ws = built.smsut_conv2d_wgrad_mfma_ws(32, 256, 256, 16, 16, 3)
     assert ws % (9 * 16 * 16) == 0 and 0 < ws // (9 * 16 * 16) <= 1024
     ws_big = built.smsut_conv2d_wgrad_mfma_ws(32, 16, 16, 256, 256, 3)
-    assert ws_big * 4 <= 32 << 20            # split slabs stay bounded (SMSUT_WGRAD_CAP_MFLOATS, default 8M floats)
+    assert ws_big * 4 <= 32 << 20            # split slabs stay bounded (WGRAD_CAP_MFLOATS in conv_mfma.hip: 8M floats)
     assert built.smsut_in_chunks(32, 65536, 16) >= 32
 
 
@@ -134,3 +134,37 @@ def test_weight_gradient_workspace_covers_every_kernel_plan():
     assert lib.smsut_conv2d_wgrad_sc_supported(16, 256, 256, 32, 16) == 1            # r04: the register-row kernel carries the extra tile
     assert lib.smsut_conv2d_wgrad_sc_supported(16, 128, 128, 16, 32) == 1
     assert lib.smsut_conv2d_wgrad_sc_supported(16, 256, 256, 48, 80) == 0
+
+
+# Environment switches whose experiments ended: the library and the package read none of them any more.
+_RETIRED_ENV = """
+    CONV_PERSISTENT CONV_K8 CONV_N8 DENSE_PLANES F16_CK32 FUSE_SHORTCUT FUSE_SHORTCUT_F16 FUSE_SHORTCUT_DGRAD
+    FUSE_SHORTCUT_DGRAD_F16 FUSE_SHORTCUT_WGRAD FUSE_SHORTCUT_WGRAD_F16 F16_STORE PLANE_WGRAD WGRAD_PAIR WGRAD_RR WINOGRAD_L
+    CONVT_PS STEM IN_ONE_CHUNK IN_SLABS WINOGRAD_WG F16_TH16 CFG_F16 WINO_L_MIN_K WGRAD_TARGET11 WGRAD_TARGET
+    WGRAD_CAP_MFLOATS RR_TARGET RR_TARGET4 RR_RCMAX IN_SLAB_WGS WINO_WGS_PER_CU CUS P_WGS_PER_CU WINO_NTN RR_V32 LOG_CONV
+    ONE_PASS_CONCAT INAFF_CONV2 POOL_SKIP THIN_1X1 REMASK_TAIL FUSED_BWD_STATS HS_INAFF INAFF_MIN_CO FIN_MASK
+    FORCE_GENERIC_CONV WINO_PREPARED""".split()
+_RETIRED_OPS_FLAGS = """ONE_PASS_CONCAT INAFF_CONV2 POOL_SKIP THIN_1X1 REMASK_TAIL FUSED_BWD_STATS HS_INAFF F16_STORE INAFF_MIN_CO
+    FIN_MASK FORCE_GENERIC_CONV WINO_PREPARED""".split()
+
+
+def test_library_reads_one_environment_variable():
+    """Which kernel runs depends on the call's arguments alone, except for SMSUT_WINOGRAD (the direct forms as the reference the
+    Winograd forms are tested against): ``getenv`` appears once in csrc/, inside that helper, and no retired switch is named in
+    csrc/ or in the package's Python files."""
+    pkg = os.path.dirname(ge.CSRC)
+    csrc = {f: open(os.path.join(ge.CSRC, f)).read() for f in sorted(os.listdir(ge.CSRC)) if f.endswith((".hip", ".h"))}
+    calls = [(f, ln) for f, txt in csrc.items() for ln in txt.splitlines() if "getenv" in ln]
+    assert len(calls) == 1 and calls[0][0] == "common.h" and 'getenv("SMSUT_WINOGRAD")' in calls[0][1], calls
+    helper = re.search(r"inline bool winograd_on\(\) \{(.*?)\n\}", csrc["common.h"], flags=re.S)
+    assert helper and "getenv" in helper.group(1)
+    env = re.compile(r"\bSMSUT_(%s)\b" % "|".join(_RETIRED_ENV))
+    flags = re.compile(r"\b(%s)\b" % "|".join(_RETIRED_OPS_FLAGS))
+    py = {}
+    for d, _, files in os.walk(pkg):
+        py.update({os.path.join(d, f): open(os.path.join(d, f)).read() for f in files if f.endswith(".py")})
+    assert py
+    for path, txt in [*((os.path.join(ge.CSRC, f), t) for f, t in csrc.items()), *py.items()]:
+        assert not env.search(txt), (path, env.search(txt).group(0))
+        if path.endswith(".py"):
+            assert not flags.search(txt), (path, flags.search(txt).group(0))

@@ -206,7 +206,6 @@ def test_wino_prepared_scope_unwinds_on_failure_and_nests(monkeypatch):
         ws = types.SimpleNamespace(forms=forms, stale_layout=lambda mod: False)
         m.__dict__["_smsut_wino_set"] = ws
         return m
-    monkeypatch.setattr(ops, "WINO_PREPARED", True)
     monkeypatch.setattr(ops, "CONV_F16", False)
     assert not ops._WINO_ACTIVE
     good = module((Form([(1, 0), (2, 0)], 100), Form([(1, 1)], 200)))

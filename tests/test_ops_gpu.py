@@ -1,5 +1,4 @@
 """Op-level parity of every HIP kernel family (called through the C-ABI) against plain PyTorch fp32/fp64 on CPU."""
-import os
 
 import numpy as np
 import pytest
@@ -665,8 +664,6 @@ def test_input_side_instnorm_conv_bit_identical(ops, n, h, c):
     gam, bet = (1 + 0.1 * torch.randn(c, generator=g)).cuda(), (0.1 * torch.randn(c, generator=g)).cuda()
     gy = torch.randn(n, h, h, c, generator=g).cuda()
     hw = h * h
-    if os.environ.get("SMSUT_CONV_PERSISTENT", "1") == "0":
-        pytest.skip("SMSUT_CONV_PERSISTENT=0 in the environment")
     assert H.call("smsut_conv2d_mfma_persistent", n, h, h, c, c, 3, 0) == 1
     tiles = H.call("smsut_conv2d_mfma_tiles", n, h, h, c, c, 3, 0)
     E = lambda *s: torch.empty(*s, device="cuda")
