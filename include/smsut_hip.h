@@ -552,6 +552,31 @@ int smsut_patchnce_fwd(const float* q, const float* k, float* loss, float* probs
 int smsut_patchnce_bwd(const float* gloss, const float* probs, const float* k, float* gq, int rows, int np, int dim,
                        float T, void* stream);
 
+/* ---------------------------------------------------------------------------------------------- test-phase metrics
+ * The `-p test` table of trainer/baseTrainer.py:254-318: get_all_matrix (misc/utils.py:206-283) cleans every predicted volume
+ * with connected_components (misc/utils.py:18-36, skimage measure.label connectivity=2) in 3-D and then slice by slice, and
+ * scores each organ with medpy's dc and assd (unit spacing, erosion connectivity 1).  Volumes are dense uint8 [D][H][W]; a 2-D
+ * image is D = 1.  Workspaces are BYTES, from the matching *_ws query (-1 there: invalid arguments).
+ *
+ * smsut_cc_filter: out[v] = c where v lies in a component of class c in 1..n_cls (label value c; different classes never merge)
+ *   whose size S satisfies (double)S > 0.1 * (double)F, F = the class's voxel count (per_slice = 1: in that slice), else 0 --
+ *   values above n_cls become 0.  per_slice = 0: 3-D 18-neighbourhood; 1: each z slice alone, 8-neighbourhood.  out may alias in.
+ *   The first int of the workspace is an error word: 0 after a good run, non-zero if a union-find loop hit its bound of D*H*W
+ *   iterations (a bug, reported instead of hanging; out is then undefined).  D*H*W < 2^31, 1 <= n_cls <= 255.
+ * smsut_surface_stats: out = double[n_cls][7], per label l = 1..n_cls of P = (pred == l), G = (gt == l):
+ *   {|P & G|, |P|, |G|, border voxels of P, sum over them of the distance to the nearest border voxel of G,
+ *    border voxels of G, sum over them of the distance to the nearest border voxel of P}
+ *   border = mask XOR erosion(mask) with the 6-neighbour cross (4-neighbour when planar = 1, which needs D = 1) and the array
+ *   faces outside the mask; distances are exact Euclidean in voxels (fp64 sqrt of integer squared distances), reduced in a
+ *   fixed order: the result is bitwise reproducible.  A distance sum is meaningless when the other mask is empty.
+ *   D, H, W <= 4096. */
+int64_t smsut_cc_ws(int D, int H, int W, int n_cls, int per_slice);
+int smsut_cc_filter(const uint8_t* in, uint8_t* out, void* workspace, int D, int H, int W, int n_cls, int per_slice,
+                    void* stream);
+int64_t smsut_surface_ws(int D, int H, int W, int n_cls, int planar);
+int smsut_surface_stats(const uint8_t* pred, const uint8_t* gt, double* out, void* workspace, int D, int H, int W, int n_cls,
+                        int planar, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,6 +1,8 @@
 """The pieces of the reference's ``misc/utils.py`` that the hot-path trainers touch: ``Meter`` (:58-160) and
 ``maybe_mkdir``; plus the Dice matrix of ``get_mo_matrix`` (:180-203) with medpy's ``dc`` restated from its
-formula (medpy is a third-party dependency that is not installed here; SURVEY.md 8c: parity unpinned)."""
+formula (medpy is a third-party dependency that is not installed here; SURVEY.md 8c: parity unpinned), and the test
+table of ``get_all_matrix`` (:206-283) with ``connected_components`` (:18-36) and medpy's ``assd`` restated on the GPU
+(csrc/metrics.hip; skimage and medpy are not installed here either, the same unpinned parity)."""
 import os
 from collections import OrderedDict
 from copy import deepcopy
@@ -40,6 +42,109 @@ def get_mo_matrix(prd_npys, gt_npys):
     full[-1, :] = np.mean(full[0:cfg.n_modal], axis=0)
     full[:, -1] = np.mean(full[:, 0:cfg.n_label], axis=1)
     return full
+
+
+def _full_matrix(matrix, n):
+    """Per-modality average with the reference's zero guard, then the mean row and column (utils.py:196-203, :255-280)."""
+    n = n.copy()
+    n[n == 0] += 1e-8
+    matrix = matrix / n
+    full = np.zeros((cfg.n_modal + 1, cfg.n_label + 1))
+    full[:cfg.n_modal, :cfg.n_label] = matrix
+    full[-1, :] = np.mean(full[0:cfg.n_modal], axis=0)
+    full[:, -1] = np.mean(full[:, 0:cfg.n_label], axis=1)
+    return full
+
+
+def _device_u8(a, what):
+    """An integer (or bool) NumPy array with values in 0..255 as a uint8 tensor on the current HIP device."""
+    import torch
+    from .._hip import SmsutHipError
+    a = np.asarray(a)
+    if a.dtype != np.bool_ and not np.issubdtype(a.dtype, np.integer):
+        raise TypeError(f"{what}: expected an integer array, got {a.dtype}")
+    if a.size and (a.min() < 0 or a.max() > 255):
+        raise ValueError(f"{what}: values must lie in 0..255 (got {a.min()}..{a.max()})")
+    if not torch.cuda.is_available():
+        raise SmsutHipError("the test-phase metrics run on an MI355X (no HIP device visible; there is no CPU fallback)")
+    return torch.from_numpy(np.ascontiguousarray(a, dtype=np.uint8)).to(torch.device("cuda", torch.cuda.current_device()))
+
+
+def connected_components(pred):
+    """utils.py:18-36 on the GPU: for each class c = 1 .. cfg.n_modal (the reference's bound, ``range(cfg.n_modal)``, not
+    n_label; both are 4 in config.py) label the components of ``pred == c`` with skimage's connectivity=2 (18-neighbour in
+    3-D, 8-neighbour in 2-D) and keep those of more than 0.1 * (voxels of class c) voxels (fp64 comparison; a component of
+    exactly a tenth is dropped).  Kept voxels hold c, all others 0 (values above n_modal too).  2-D or 3-D integer array in
+    0..255 -> uint8 array of the same shape."""
+    from .. import ops
+    t = _device_u8(pred, "connected_components")
+    if t.dim() not in (2, 3):
+        raise ValueError(f"connected_components: expected a 2-D or 3-D array, got shape {tuple(t.shape)}")
+    return ops.cc_filter(t, cfg.n_modal, per_slice=False).cpu().numpy()
+
+
+def assd(result, reference):
+    """medpy.metric.binary.assd with its defaults (unit spacing, erosion connectivity 1) on the GPU: the mean of the two
+    average surface distances, each the mean over one mask's border voxels (mask XOR its erosion by the 6-neighbour cross,
+    array faces outside) of the exact Euclidean distance to the other mask's border.  2-D or 3-D masks (nonzero = in);
+    ``RuntimeError`` when either is empty, as medpy raises."""
+    from .. import ops
+    a = _device_u8(np.asarray(result).astype(bool), "assd")
+    b = _device_u8(np.asarray(reference).astype(bool), "assd")
+    if a.shape != b.shape or a.dim() not in (2, 3):
+        raise ValueError(f"assd: expected two 2-D or 3-D masks of one shape, got {tuple(a.shape)} and {tuple(b.shape)}")
+    st = ops.surface_stats(a, b, 1)[0]
+    if st[1] == 0:
+        raise RuntimeError("The first supplied array does not contain any binary object.")
+    if st[2] == 0:
+        raise RuntimeError("The second supplied array does not contain any binary object.")
+    return 0.5 * (st[4] / st[3] + st[6] / st[5])
+
+
+def get_all_matrix(prd_npys, gt_npys):
+    """utils.py:206-283: (Dice, "Hausdorff", ASSD) modality x organ matrices, each (n_modal + 1) x (n_label + 1) with the
+    mean row and column.  Per volume: connected_components in 3-D, then on every z slice alone (its own class totals);
+    per organ j the Dice of the cleaned prediction and, if the prediction holds j, its ASSD to the ground truth -- else the
+    running maximum of the ASSDs of this volume's earlier organs (0 for the first).  An empty ground truth under a
+    non-empty prediction raises RuntimeError, as in the reference.  The second matrix is the reference's placeholder
+    (``t = s``, its hd call commented out): a copy of the Dice values.  Each volume is uploaded once; cleanup and surface
+    statistics run on the device."""
+    from .. import ops
+    matrix = np.zeros((cfg.n_modal, cfg.n_label))
+    hd_matrix = np.zeros((cfg.n_modal, cfg.n_label))
+    assd_matrix = np.zeros((cfg.n_modal, cfg.n_label))
+    n = np.zeros((cfg.n_modal, 1))
+    for k in gt_npys.keys():
+        m = cfg.Modality[k.split("_")[0]].value
+        p = _device_u8(prd_npys[k], f"prediction {k}")
+        g = _device_u8(gt_npys[k], f"ground truth {k}")
+        if p.dim() != 3 or p.shape != g.shape:
+            raise ValueError(f"{k}: expected two [D, H, W] volumes of one shape, got {tuple(p.shape)} and {tuple(g.shape)}")
+        p1 = ops.cc_filter(p, cfg.n_modal, per_slice=False)
+        p1 = ops.cc_filter(p1, cfg.n_modal, per_slice=True)
+        st = ops.surface_stats(p1, g, cfg.n_label)
+        maxassd = 0
+        for i in range(cfg.n_label):
+            inter, n_p, n_g, b_p, s_p, b_g, s_g = st[i]
+            den = n_p + n_g
+            s = 2.0 * inter / float(den) if den else 0.0
+            if n_p == 0:
+                r = maxassd
+            elif n_g == 0:
+                raise RuntimeError("The second supplied array does not contain any binary object.")
+            else:
+                r = 0.5 * (s_p / b_p + s_g / b_g)
+            maxassd = maxassd if maxassd > r else r
+            matrix[m][i] += s
+            hd_matrix[m][i] += s
+            assd_matrix[m][i] += r
+        n[m] += 1
+    return _full_matrix(matrix, n), _full_matrix(hd_matrix, n), _full_matrix(assd_matrix, n)
+
+
+def matrix_text(matrix):
+    """Rows of '%.4f' values joined by ',' (the layout of the reference's ``{modality}_trois_matrix.csv``)."""
+    return "".join(",".join("%.4f" % v for v in row) + "\n" for row in matrix)
 
 
 class Meter:

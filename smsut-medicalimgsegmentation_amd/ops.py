@@ -2200,3 +2200,48 @@ def row_lerp(a, b, alpha):
     H.call("smsut_row_lerp", a, b, alpha.detach().reshape(-1).contiguous().to(torch.float32), out, rows,
            a.numel() // rows, _s())
     return out
+
+
+# ------------------------------------------------------------------------------------------- test-phase metrics
+def _dhw(vol: torch.Tensor):
+    """(D, H, W, planar) of a dense uint8 volume [D, H, W] or image [H, W] on the device."""
+    if vol.dtype != torch.uint8 or vol.dim() not in (2, 3):
+        raise ValueError(f"expected a uint8 [H, W] or [D, H, W] tensor, got {vol.dtype} {tuple(vol.shape)}")
+    return (1, *vol.shape, 1) if vol.dim() == 2 else (*vol.shape, 0)
+
+
+def _byte_ws(nbytes: int, like: torch.Tensor) -> torch.Tensor:
+    if nbytes < 0:
+        raise H.SmsutHipError("invalid metrics arguments (workspace query returned -1)")
+    return torch.empty(max(int(nbytes), 4), dtype=torch.uint8, device=like.device)
+
+
+def cc_filter(vol_u8, n_cls, per_slice):
+    """Connected-component cleanup of classes 1..n_cls (reference misc/utils.py:18-36): components of at most a tenth of their
+    class's voxels are dropped, everything else above n_cls becomes 0.  ``per_slice``: 8-neighbour labelling of each z slice
+    alone; else 18-neighbour 3-D labelling.  Returns a new uint8 tensor; raises ``SmsutHipError`` if the labelling reported
+    its loop bound (waits for the device to read the error word)."""
+    vol = vol_u8.contiguous()
+    d, h, w, _ = _dhw(vol)
+    per_slice = int(bool(per_slice))
+    ws = _byte_ws(H.call("smsut_cc_ws", d, h, w, int(n_cls), per_slice), vol)
+    out = torch.empty_like(vol)
+    H.call("smsut_cc_filter", vol, out, ws, d, h, w, int(n_cls), per_slice, _s())
+    err = int(ws[:4].view(torch.int32).item())
+    if err:
+        raise H.SmsutHipError(f"smsut_cc_filter: union-find loop bound reached (error word {err})")
+    return out
+
+
+def surface_stats(pred_u8, gt_u8, n_cls):
+    """Per label 1..n_cls: float64 host array [n_cls, 7] = {|P&G|, |P|, |G|, border(P), sum dist(border P -> border G),
+    border(G), sum dist(border G -> border P)} (medpy's dc / assd ingredients at unit spacing, erosion connectivity 1)."""
+    pred, gt = pred_u8.contiguous(), gt_u8.contiguous()
+    if pred.shape != gt.shape:
+        raise ValueError(f"shape mismatch {tuple(pred.shape)} vs {tuple(gt.shape)}")
+    d, h, w, planar = _dhw(pred)
+    _dhw(gt)
+    ws = _byte_ws(H.call("smsut_surface_ws", d, h, w, int(n_cls), planar), pred)
+    out = torch.empty(int(n_cls), 7, dtype=torch.float64, device=pred.device)
+    H.call("smsut_surface_stats", pred, gt, out, ws, d, h, w, int(n_cls), planar, _s())
+    return out.cpu().numpy()

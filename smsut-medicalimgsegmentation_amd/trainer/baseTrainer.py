@@ -22,7 +22,7 @@ from .. import config as cfg
 from .. import ops, parallel
 from ..misc.loss import DiceAndCrossEntropyLoss
 from ..misc.synthetic import SyntheticSliceLoader
-from ..misc.utils import Meter, get_mo_matrix, maybe_mkdir
+from ..misc.utils import Meter, get_all_matrix, get_mo_matrix, matrix_text, maybe_mkdir
 
 
 def seed_all(seed=None):
@@ -408,13 +408,20 @@ class BaseTrainer(abc.ABC):
         return d
 
     def test(self, loader_type, expr_root):
-        """baseTrainer.py:254-318 minus ASSD / connected components (third-party CPU post-processing, out of scope)."""
+        """baseTrainer.py:254-318: the raw Dice matrix (``dice_matrix.csv``, returned) and the reference's test table
+        ``{modality}_trois_matrix.csv`` -- the Dice rows, an empty line, then the ASSD rows of ``get_all_matrix`` (connected-
+        component cleanup + average symmetric surface distance, on the GPU), '%.4f' values separated by ','; also logged."""
         _, _, loader = self.get_loaders(loader_type)
         gt = self._collect_labels(loader)
         n, prd = self.validate_epoch(loader, gt)
         mo = get_mo_matrix(prd, gt)
         maybe_mkdir(expr_root)
         np.savetxt(pjoin(expr_root, "dice_matrix.csv"), mo, delimiter=",", fmt="%.6f")
+        _, _, assd_matrix = get_all_matrix(prd, gt)
+        log = matrix_text(mo) + "\n" + matrix_text(assd_matrix)
+        with open(pjoin(expr_root, f"{self.modality}_trois_matrix.csv"), "w") as f:
+            f.write(log)
+        self.info(log)
         return mo
 
     def close(self):
