@@ -354,6 +354,7 @@ int smsut_colsum(const float* x, float* out, float* workspace, int64_t rows, int
  * _bwd2 is the backward of _bwd, needed because WGAN-GP differentiates D's backward
  * (trainer/uganShp0Trainer.py:127-134, create_graph=True). */
 int smsut_in_chunks(int N, int HW, int C); /* workspace = N * chunks * C * 3 floats */
+int smsut_in_slabs(int N, int HW, int C);  /* channel slabs of the partial-sum launches (host-only query) */
 int smsut_instnorm_fwd(const float* x, const float* gamma, const float* beta, float* y, float* mean, float* rstd,
                        float* workspace, int N, int HW, int C, float eps, float slope, int has_act, void* stream);
 int smsut_instnorm_fwd_partials(const float* x, const float* gamma, const float* beta, float* y, float* mean,

@@ -897,6 +897,10 @@ inline int slab_count(int N, int chunks, int C, int vec) {
 extern "C" {
 
 int smsut_in_chunks(int N, int HW, int C) { return (int)cdiv64(HW, pick_chunk(HW, C, N)); }
+// channel slabs (gridDim.z) of the partial-sum launches of this shape: lets the tests check which reduction regime a case lands in
+int smsut_in_slabs(int N, int HW, int C) {
+  return slab_count(N, smsut_in_chunks(N, HW, C), C, C % 4 == 0 ? 4 : 1);
+}
 
 // workspace: float[N * smsut_in_chunks * C * 3]
 int smsut_instnorm_fwd(const float* x, const float* gamma, const float* beta, float* y, float* mean, float* rstd,
