@@ -553,6 +553,45 @@ int smsut_patchnce_fwd(const float* q, const float* k, float* loss, float* probs
 int smsut_patchnce_bwd(const float* gloss, const float* probs, const float* k, float* gq, int rows, int np, int dim,
                        float T, void* stream);
 
+/* ---------------------------------------------------------------------------------------------- CoraNet heads
+ * trainer/coraNetTrainer.py after the logits.  The 3L+1 channels of the U-Net output [N][HW][3L+1] are three (L+1)-class heads
+ * h0, h1, h2 that share the background logit (channel 0; head k owns channels 1+kL .. (k+1)L), 1 <= L <= 10.  No head is ever
+ * materialised: every pass reads a pixel's logits once and the backward passes write its 3L+1 gradients once.
+ * workspace (both statistics passes): smsut_cora_ws(N, HW, L) floats.
+ *
+ * Supervised loss (:288-301), two stages like smsut_dicece_*:
+ *   S = ([w_dc Dice_batch(h0, y) + w_ce CE(h0, y)] + CE_{w_con}(h1, y) + CE_{w_rad}(h2, y)) / 4,
+ *   CE_w = sum_p w[y_p] nll_p / sum_p w[y_p] (torch CrossEntropyLoss(weight=w)); w_con, w_rad: device arrays of L+1 floats.
+ *   stats[3(L+1)+3] = head-0 {tp, sum_p, count}[L+1], sum nll(h0), sum w_con[y] nll(h1), sum w_rad[y] nll(h2): sums over the batch, so
+ *   under data parallelism the caller all-reduces them between the stages and passes the global pixel count.
+ *   final: out[4] = [S, w_dc dice + w_ce ce of head 0, CE_con, CE_rad];  bwd: glogits = gout[0] * dS/dlogits.
+ * Pseudo-labelled loss (:304-347) of student logits z against pseudo labels q, mask m in {0,1} and teacher logits e:
+ *   certain   = (sum_p m_p nll_p(h0, q) / (sum_p m_p + 1e-16) + Dice_per_sample(h0, q)) / 2
+ *   uncertain = (cw / 3) sum_k [sum_p (1 - m_p) |softmax(h_k(z)) - softmax(h_k(e))|^2 / (sum_p (1 - m_p) + 1e-16)]
+ *   stats[N][3(L+1)+4] per sample = head-0 {tp, sum_p, count}[L+1] against q, sum m nll, sum m, the masked squared-difference sum over
+ *   the three heads, sum (1 - m).  final: out[2] = [certain, uncertain];  bwd: gz = gout[0] d certain/dz + gout[1] d uncertain/dz
+ *   (no gradient to e).
+ * smsut_cora_pseudo: q[p] = argmax(h0) (int64), m[p] = (argmax(h1) == argmax(h2)) (0/1), first maximum wins (:189-208). */
+int64_t smsut_cora_ws(int N, int64_t HW, int L);
+int smsut_cora_sup_stats(const float* logits, const int64_t* labels, const float* w_con, const float* w_rad, float* stats,
+                         float* workspace, int N, int64_t HW, int L, void* stream);
+int smsut_cora_sup_final(const float* stats, const float* w_con, const float* w_rad, float* out /*4*/, int L, double npix_total,
+                         float w_dc, float w_ce, void* stream);
+int smsut_cora_sup_bwd(const float* logits, const int64_t* labels, const float* stats, const float* w_con, const float* w_rad,
+                       const float* gout, float* glogits, int N, int64_t HW, int L, double npix_total, float w_dc, float w_ce,
+                       void* stream);
+int smsut_cora_semi_stats(const float* z, const float* e, const int64_t* q, const float* m, float* stats, float* workspace, int N,
+                          int64_t HW, int L, void* stream);
+int smsut_cora_semi_final(const float* stats, float* out /*2*/, int N, int L, float cw, void* stream);
+int smsut_cora_semi_bwd(const float* z, const float* e, const int64_t* q, const float* m, const float* stats, const float* gout /*2*/,
+                        float* gz, int N, int64_t HW, int L, float cw, void* stream);
+int smsut_cora_pseudo(const float* z, int64_t* q, float* m, int64_t P, int L, void* stream);
+/* ema = alpha * ema + beta * p over many tensors in one launch (:168-174; beta = 1 - alpha).  ents: device array of
+ * {float* ema, const float* p, int64 n}; blk_ent / blk_chunk: for every block its entry and its chunk of smsut_ema_chunk() elements
+ * inside that entry's tensor, as smsut_sgd_momentum_multi. */
+int smsut_ema_multi(const void* ents, const int* blk_ent, const int* blk_chunk, int nblocks, float alpha, float beta, void* stream);
+int smsut_ema_chunk(void);
+
 /* ---------------------------------------------------------------------------------------------- test-phase metrics
  * The `-p test` table of trainer/baseTrainer.py:254-318: get_all_matrix (misc/utils.py:206-283) cleans every predicted volume
  * with connected_components (misc/utils.py:18-36, skimage measure.label connectivity=2) in 3-D and then slice by slice, and

@@ -205,6 +205,17 @@ SIGNATURES: Dict[str, str] = {
     "smsut_l2norm_bwd": "pppp ii s",
     "smsut_patchnce_fwd": "pppp iii f s",
     "smsut_patchnce_bwd": "pppp iii f s",
+    # coranet.hip
+    "smsut_cora_ws": "i l i",
+    "smsut_cora_sup_stats": "pppppp i l i s",
+    "smsut_cora_sup_final": "pppp i d ff s",
+    "smsut_cora_sup_bwd": "ppppppp i l i d ff s",
+    "smsut_cora_semi_stats": "pppppp i l i s",
+    "smsut_cora_semi_final": "pp ii f s",
+    "smsut_cora_semi_bwd": "ppppppp i l i f s",
+    "smsut_cora_pseudo": "ppp l i s",
+    "smsut_ema_multi": "ppp i ff s",
+    "smsut_ema_chunk": "",
     # metrics.hip (test phase)
     "smsut_cc_ws": "iiiii",
     "smsut_cc_filter": "ppp iiiii s",
@@ -213,7 +224,7 @@ SIGNATURES: Dict[str, str] = {
 }
 _RET_I64 = {"smsut_wino_image_floats", "smsut_conv2d_wgrad_pair_ws", "smsut_convT2x2_wgrad_ps_ws", "smsut_conv2d_wgrad_sc_ws", "smsut_conv2d_k4_wgrad_ws", "smsut_conv2d_wgrad_f16_ws", "smsut_conv2d_wgrad_sc_f16_ws", "smsut_absmax_scale_ws", "smsut_conv2d_wgrad_generic_ws", "smsut_colsum_ws", "smsut_dicece_ws", "smsut_sum_ws",
             "smsut_conv2d_wgrad_mfma_ws", "smsut_convT2x2_wgrad_mfma_ws", "smsut_conv2d_flat_wgrad_ws", "smsut_conv1x1_wgrad_ws",
-            "smsut_conv1x1_thin_wgrad_ws", "smsut_cc_ws", "smsut_surface_ws"}
+            "smsut_conv1x1_thin_wgrad_ws", "smsut_cc_ws", "smsut_surface_ws", "smsut_cora_ws"}
 _NO_STATUS = _RET_I64 | {"smsut_conv2d_k4_supported", "smsut_conv2d_f16_supported", "smsut_conv2d_wgrad_f16_supported", "smsut_in_chunks", "smsut_in_slabs", "smsut_amax_blocks", "smsut_conv2d_mfma_supported", "smsut_conv2d_wgrad_mfma_supported",
                          "smsut_convT2x2_mfma_supported", "smsut_conv2d_small_supported",
                          "smsut_conv2d_flat_wgrad_supported", "smsut_conv2d_mfma_tiles", "smsut_conv2d_mfma_persistent", "smsut_conv1x1_supported",
@@ -221,7 +232,7 @@ _NO_STATUS = _RET_I64 | {"smsut_conv2d_k4_supported", "smsut_conv2d_f16_supporte
                          "smsut_conv2d_fwd_sc_supported", "smsut_conv2d_fwd_sc_f16_supported", "smsut_conv2d_dgrad_sc_supported",
                          "smsut_conv2d_dgrad_sc_f16_supported", "smsut_conv2d_wgrad_sc_f16_supported", "smsut_conv2d_f16_hs_supported",
                          "smsut_conv2d_wgrad_sc_supported", "smsut_convT2x2_ps_supported", "smsut_conv2d_wgrad_pair_supported",
-                         "smsut_conv2d_wgrad_mfma_slabs", "smsut_conv2d_wgrad_pair_slabs", "smsut_conv2d_mfma_form", "smsut_sgd_chunk"}     # (return a count / a form id, not a status)
+                         "smsut_conv2d_wgrad_mfma_slabs", "smsut_conv2d_wgrad_pair_slabs", "smsut_conv2d_mfma_form", "smsut_sgd_chunk", "smsut_ema_chunk"}     # (return a count / a form id, not a status)
 
 _CT = {"p": ctypes.c_void_p, "i": ctypes.c_int, "l": ctypes.c_int64, "f": ctypes.c_float, "d": ctypes.c_double,
        "s": ctypes.c_void_p}

@@ -32,6 +32,22 @@ lr = 1e-2                      # config.py:73-74
 weight_decay = 1e-3
 nce_layers = [5]               # config.py:77
 
+# CoraNet (config.py:80-94).  The reference ships two-class weight vectors with the CHAOS values in comments ([1, 5, 5, 5, 5] /
+# [5, 1, 1, 1, 1]); here they are (background, foreground) pairs, expanded to n_label + 1 entries when the trainer is built.
+thres = 0.5
+default_w = (1.0, 1.0)
+w_con = (1.0, 5.0)
+w_rad = (5.0, 1.0)
+pre_epoch = 100
+cora_epoch = 200
+pred_step = 10
+
+
+def class_weights(pair, labels=None):
+    """``[background] + [foreground] * labels``: a (background, foreground) weight pair as the per-class vector of
+    ``nn.CrossEntropyLoss(weight=...)``; ``labels`` defaults to the current ``n_label`` (read at call time: tests change it)."""
+    return [float(pair[0])] + [float(pair[1])] * (n_label if labels is None else labels)
+
 expr_root = "smsut_out"        # the reference's placeholder is '***/bimod-out' (config.py:46)
 base_root = None               # processed PNG dataset root ('***/bimod' upstream, config.py:44); None -> synthetic slices
 split_yaml = "semi-1910.yaml"  # config.py:54

@@ -2056,6 +2056,182 @@ def argmax_channels(logits):
     return out
 
 
+# ------------------------------------------------------------------------------------------- CoraNet heads
+# The 3L+1 channels of the CoraNet U-Net are three (L+1)-class heads sharing the background logit (channel 0; head k owns channels
+# 1+kL .. (k+1)L, reference trainer/coraNetTrainer.py:288-295).  These ops take the network's NHWC output as it is -- no concatenated
+# head copy anywhere (csrc/coranet.hip).
+def _cora_heads(logits, what):
+    c = logits.shape[1]
+    if c < 4 or (c - 1) % 3:
+        raise ValueError(f"{what}: expected 3L+1 channels, got {c}")
+    return (c - 1) // 3
+
+
+def _cora_weights(w, n_cls, like):
+    if w.dtype != torch.float32 or w.numel() != n_cls or w.device != like.device:
+        raise ValueError(f"class weights must be {n_cls} fp32 values on {like.device}")
+    return w.contiguous()
+
+
+def _cora_labels(t, logits, dtype, what):
+    n, _, h, w = logits.shape
+    if t.dtype != dtype or tuple(t.shape) != (n, h, w):
+        raise TypeError(f"{what} must be {dtype} of shape {(n, h, w)}, got {t.dtype} {tuple(t.shape)}")
+    return t.contiguous()
+
+
+def cora_sup_stats(logits, labels, w_con, w_rad):
+    """Stage 1 of the supervised head loss: one pass over the logits -> flat statistics [3(L+1)+3] of the three heads (batch sums:
+    all-reduced by the caller under data parallelism, like the Dice statistics).  No autograd."""
+    logits = nhwc(logits.detach())
+    L = _cora_heads(logits, "cora_sup_stats")
+    n, c, h, w = logits.shape
+    labels = _cora_labels(labels, logits, torch.int64, "labels")
+    stats = torch.empty(3 * (L + 1) + 3, dtype=torch.float32, device=logits.device)
+    H.call("smsut_cora_sup_stats", logits, labels, _cora_weights(w_con, L + 1, logits), _cora_weights(w_rad, L + 1, logits), stats,
+           _ws(H.call("smsut_cora_ws", n, h * w, L), logits), n, h * w, L, _s())
+    return stats
+
+
+class CoraSupFromStatsFn(Function):
+    """Stage 2: [S, dice+ce of head 0, con, rad] from (already global) statistics; element 0 is the loss and the only one that carries
+    a gradient (the backward reads d/dS alone).  ``world`` as in ``DiceCEFromStatsFn``: all three terms are ratios of global sums, so
+    this rank's backward is its share of the global loss and is scaled by ``world`` ahead of the averaging gradient all-reduce."""
+
+    @staticmethod
+    def forward(ctx, logits, labels, stats, w_con, w_rad, w_ce, w_dc, world):
+        logits = nhwc(logits)
+        L = _cora_heads(logits, "cora_sup_loss")
+        n, c, h, w = logits.shape
+        npix = float(n * h * w) * world
+        w_con, w_rad = _cora_weights(w_con, L + 1, logits), _cora_weights(w_rad, L + 1, logits)
+        out = torch.empty(4, dtype=torch.float32, device=logits.device)
+        H.call("smsut_cora_sup_final", stats, w_con, w_rad, out, L, npix, float(w_dc), float(w_ce), _s())
+        ctx.save_for_backward(logits, _cora_labels(labels, logits, torch.int64, "labels"), stats, w_con, w_rad)
+        ctx.cfg = (L, npix, float(w_dc), float(w_ce), int(world))
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gout):
+        logits, labels, stats, w_con, w_rad = ctx.saved_tensors
+        L, npix, w_dc, w_ce, world = ctx.cfg
+        n, c, h, w = logits.shape
+        gl = new_act(n, c, h, w, logits)
+        gout = gout.contiguous()
+        if world > 1:
+            gout = gout * float(world)
+        H.call("smsut_cora_sup_bwd", logits, labels, stats, w_con, w_rad, gout, gl, n, h * w, L, npix, w_dc, w_ce, _s())
+        return gl, None, None, None, None, None, None, None
+
+
+def cora_sup_loss(logits, labels, w_con, w_rad, weight_ce, weight_dc, group=None):
+    """Supervised CoraNet loss on logits [N, 3L+1, H, W] / int64 labels [N, H, W] (reference trainer/coraNetTrainer.py:288-301):
+    returns the device tensor ``[S, dice+ce of head 0, con, rad]`` with
+    ``S = ([weight_dc Dice_batch(h0) + weight_ce CE(h0)] + CE_{w_con}(h1) + CE_{w_rad}(h2)) / 4``; differentiate ``[0]``.
+    ``w_con`` / ``w_rad``: fp32 device tensors of L+1 class weights.  ``group``: the statistics are all-reduced between the two stages
+    (one collective, ``all_reduce_dice_stats``) so the value is the single-process global-batch loss."""
+    stats = cora_sup_stats(logits, labels, w_con, w_rad)
+    world = 1
+    if group is not None:
+        import torch.distributed as dist
+        world = dist.get_world_size(group)
+        if world > 1:
+            all_reduce_dice_stats([(stats,)], group)
+    return CoraSupFromStatsFn.apply(logits, labels, stats, w_con, w_rad, weight_ce, weight_dc, world)
+
+
+class CoraSemiFn(Function):
+    """[certain, uncertain] of the pseudo-labelled half (reference trainer/coraNetTrainer.py:304-341); gradient to the student logits."""
+
+    @staticmethod
+    def forward(ctx, z, e, plab, mask, cw):
+        z, e = nhwc(z), nhwc(e)
+        if z.shape != e.shape:
+            raise ValueError(f"student / teacher logits differ in shape: {tuple(z.shape)} vs {tuple(e.shape)}")
+        L = _cora_heads(z, "cora_semi_loss")
+        n, c, h, w = z.shape
+        plab = _cora_labels(plab, z, torch.int64, "pseudo labels")
+        mask = _cora_labels(mask, z, torch.float32, "mask")
+        stats = torch.empty(n, 3 * (L + 1) + 4, dtype=torch.float32, device=z.device)
+        H.call("smsut_cora_semi_stats", z, e, plab, mask, stats, _ws(H.call("smsut_cora_ws", n, h * w, L), z), n, h * w, L, _s())
+        out = torch.empty(2, dtype=torch.float32, device=z.device)
+        H.call("smsut_cora_semi_final", stats, out, n, L, float(cw), _s())
+        ctx.save_for_backward(z, e, plab, mask, stats)
+        ctx.cfg = (L, float(cw))
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gout):
+        z, e, plab, mask, stats = ctx.saved_tensors
+        L, cw = ctx.cfg
+        n, c, h, w = z.shape
+        gz = new_act(n, c, h, w, z)
+        H.call("smsut_cora_semi_bwd", z, e, plab, mask, stats, gout.contiguous(), gz, n, h * w, L, cw, _s())
+        return gz, None, None, None, None
+
+
+def cora_semi_loss(logits, ema_logits, plab, mask, cw):
+    """Pseudo-labelled CoraNet loss: the device tensor ``[certain, uncertain]`` of student logits against pseudo labels ``plab``
+    (int64 [N, H, W]), certainty mask ``mask`` (fp32 0/1 [N, H, W]) and the teacher's logits (no gradient), consistency weight ``cw``:
+    ``certain = (masked CE(h0, plab) + Dice_per_sample(h0, plab)) / 2``, ``uncertain = cw / 3 * sum_k`` softmax-MSE of head k over the
+    pixels where the mask is 0 (both ratios count pixels).  The ratios are per rank under data parallelism, like ``softmax_mse``."""
+    return CoraSemiFn.apply(cl(logits), cl(ema_logits).detach(), plab, mask, cw)
+
+
+def cora_pseudo(logits):
+    """Pseudo labels and certainty mask in one pass (reference trainer/coraNetTrainer.py:189-208, there through numpy on the host):
+    ``(argmax(h0) int64 [N, H, W], (argmax(h1) == argmax(h2)) fp32 [N, H, W])``, first maximum wins as ``torch.argmax``."""
+    z = nhwc(logits.detach())
+    L = _cora_heads(z, "cora_pseudo")
+    n, c, h, w = z.shape
+    q = torch.empty(n, h, w, dtype=torch.int64, device=z.device)
+    m = torch.empty(n, h, w, dtype=torch.float32, device=z.device)
+    H.call("smsut_cora_pseudo", z, q, m, n * h * w, L, _s())
+    return q, m
+
+
+def _dense(t):
+    """Every element of the storage span belongs to exactly one index (any dimension order)."""
+    exp = 1
+    for size, stride in sorted(((s, st) for s, st in zip(t.shape, t.stride()) if s > 1), key=lambda x: x[1]):
+        if stride != exp:
+            return False
+        exp *= size
+    return True
+
+
+_EMA_TABLE = {}          # device -> (key, entries, blk_ent, blk_chunk, nblocks): the pointer table of the last parameter set
+
+
+def ema_update(ema_params, params, alpha):
+    """``ema = alpha * ema + (1 - alpha) * p`` over all parameter tensors in ONE launch (reference trainer/coraNetTrainer.py:168-174).
+    Each pair must be fp32, dense and of one layout (the weights' HWIO strides on both sides).  The device pointer table is rebuilt
+    only when a pointer changes."""
+    ema_params, params = list(ema_params), [p.detach() for p in params]
+    if len(ema_params) != len(params) or not params:
+        raise ValueError("ema_update needs two parameter lists of equal, non-zero length")
+    for e, p in zip(ema_params, params):
+        if (e.dtype != torch.float32 or p.dtype != torch.float32 or e.shape != p.shape or e.device != p.device
+                or any(a != b for a, b, s in zip(e.stride(), p.stride(), e.shape) if s > 1) or not _dense(e)):
+            raise ValueError(f"ema_update: tensors of shape {tuple(e.shape)} / {tuple(p.shape)} differ in dtype, device or layout")
+    dev = params[0].device
+    key = tuple((H.ptr(e), H.ptr(p), e.numel()) for e, p in zip(ema_params, params))
+    tab = _EMA_TABLE.get(dev)
+    if tab is None or tab[0] != key:
+        chunk = H.call("smsut_ema_chunk")
+        blk_ent, blk_chunk = [], []
+        for i, ent in enumerate(key):
+            nb = (ent[2] + chunk - 1) // chunk
+            blk_ent += [i] * nb
+            blk_chunk += list(range(nb))
+        tab = (key, torch.tensor(key, dtype=torch.int64, device=dev), torch.tensor(blk_ent, dtype=torch.int32, device=dev),
+               torch.tensor(blk_chunk, dtype=torch.int32, device=dev), len(blk_ent))
+        _EMA_TABLE[dev] = tab
+    H.call("smsut_ema_multi", tab[1], tab[2], tab[3], tab[4], float(alpha), float(1 - alpha), _s())
+
+
 class CERowsFn(Function):
     """F.cross_entropy(logits[B,C], target[B]) (modality classification, uganConsisTrainer.py:131,155)."""
 

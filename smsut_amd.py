@@ -27,7 +27,7 @@ def _load():
 _DROPIN = ("config", "network", "network.blocks", "network.unet", "network.ugan", "network.networks",
            "network.patchnce", "misc", "misc.loss", "misc.utils", "trainer", "trainer.baseTrainer",
            "trainer.unetTrainer", "trainer.uganShp0Trainer", "trainer.uganConsisTrainer", "trainer.uganTrainer",
-           "trainer.meanTeacherTrainer", "trainer.crossPseTrainer")
+           "trainer.meanTeacherTrainer", "trainer.crossPseTrainer", "trainer.coraNetTrainer")
 
 
 def install_dropin():
