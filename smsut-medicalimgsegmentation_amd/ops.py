@@ -15,7 +15,8 @@ with other differentiable Functions), because WGAN-GP differentiates D's backwar
 from __future__ import annotations
 
 import contextlib
-from typing import Optional
+import os as _os
+from typing import NamedTuple, Optional
 
 import torch
 from torch.autograd import Function
@@ -24,8 +25,6 @@ from torch.autograd.function import once_differentiable
 from . import _hip as H
 
 IN_EPS = 1e-5
-
-import os as _os
 
 _INPUT_GRADS_ONLY = False
 
@@ -335,6 +334,11 @@ def _s():
     return H.stream_ptr()
 
 
+def _vec(like: torch.Tensor, *shape) -> torch.Tensor:
+    """Uninitialised fp32 tensor on ``like``'s device: per-image / per-channel statistics and their gradients."""
+    return torch.empty(*shape, dtype=torch.float32, device=like.device)
+
+
 # ------------------------------------------------------------------------------------------- convolution
 def _out_size(h, k, stride, pad):
     return (h + 2 * pad - k) // stride + 1
@@ -632,8 +636,7 @@ class InstNormActFn(Function):
         x = nhwc(x)
         n, c, h, w = x.shape
         y = new_act(n, c, h, w, x)
-        mean = torch.empty(n, c, dtype=torch.float32, device=x.device)
-        rstd = torch.empty_like(mean)
+        mean, rstd = _vec(x, n, c), _vec(x, n, c)
         fused = getattr(x, "_smsut_in_partials", None)
         if fused is not None:
             part, tiles = fused
@@ -672,10 +675,8 @@ class InstNormActBwdFn(Function):
         gy = nhwc(gy)
         n, c, h, w = x.shape
         gx = new_act(n, c, h, w, x)
-        a = torch.empty(n, c, dtype=torch.float32, device=x.device)
-        b = torch.empty_like(a)
-        gg = torch.empty(c, dtype=torch.float32, device=x.device)
-        gb = torch.empty_like(gg)
+        a, b = _vec(x, n, c), _vec(x, n, c)
+        gg, gb = _vec(x, c), _vec(x, c)
         chunks = H.call("smsut_in_chunks", n, h * w, c)
         H.call("smsut_instnorm_bwd", gy, x, beta if has_act else None, mean, rstd, gamma, gx, a, b,
                gg if want_affine else None, gb if want_affine else None, _ws(n * chunks * c * 3, x),
@@ -719,8 +720,7 @@ class InstNormActPoolFn(Function):
         part, tiles = x._smsut_in_partials
         del x._smsut_in_partials
         y = new_act(n, c, h // 2, w // 2, x)
-        mean = torch.empty(n, c, dtype=torch.float32, device=x.device)
-        rstd = torch.empty_like(mean)
+        mean, rstd = _vec(x, n, c), _vec(x, n, c)
         H.call("smsut_instnorm_pool_fwd_partials", x, gamma, beta, y, mean, rstd, part, tiles, n, h, w, c, IN_EPS, float(slope), _s())
         ctx.save_for_backward(x, mean, rstd, gamma, beta)
         ctx.slope = float(slope)
@@ -734,9 +734,8 @@ class InstNormActPoolFn(Function):
         n, c, h, w = x.shape
         want_affine = (ctx.needs_input_grad[1] or ctx.needs_input_grad[2]) and not _INPUT_GRADS_ONLY
         gx = new_act(n, c, h, w, x)
-        a = torch.empty(n, c, dtype=torch.float32, device=x.device)
-        b = torch.empty_like(a)
-        gg = torch.empty(c, dtype=torch.float32, device=x.device) if want_affine else None
+        a, b = _vec(x, n, c), _vec(x, n, c)
+        gg = _vec(x, c) if want_affine else None
         gb = torch.empty_like(gg) if want_affine else None
         chunks = H.call("smsut_in_chunks", n, h * w, c)
         H.call("smsut_instnorm_pool_bwd", gy, x, beta, mean, rstd, gamma, gx, a, b, gg, gb, _ws(n * chunks * c * 3, x), n, h, w, c,
@@ -781,8 +780,7 @@ class ResTailFn(Function):
         st = _s()
 
         def stats(t):
-            m = torch.empty(n, c, dtype=torch.float32, device=t.device)
-            r = torch.empty_like(m)
+            m, r = _vec(t, n, c), _vec(t, n, c)
             part, tiles = t._smsut_in_partials            # res_tail_fusable() checked that both inputs carry them
             del t._smsut_in_partials
             H.call("smsut_in_finalize_fwd", part, tiles, m, r, n, hw, c, IN_EPS, st)
@@ -812,11 +810,9 @@ class ResTailFn(Function):
         mp = ctx.pool and g_pooled is not None
         g_out = nhwc(g_out)
         hw = h * w
-        dev = y2.device
-        vec = lambda *sh: torch.empty(*sh, dtype=torch.float32, device=dev)
         gy2, gs_t = new_act(n, c, h, w, y2), new_act(n, c, h, w, y2)
-        a_t, b2_t, bs_t = vec(n, c), vec(n, c), vec(n, c)
-        gg2, gb2, ggs, gbs = vec(c), vec(c), vec(c), vec(c)
+        a_t, b2_t, bs_t = _vec(y2, n, c), _vec(y2, n, c), _vec(y2, n, c)
+        gg2, gb2, ggs, gbs = _vec(y2, c), _vec(y2, c), _vec(y2, c), _vec(y2, c)
         chunks = H.call("smsut_in_chunks", n, hw, c)
         if mp:
             H.call("smsut_restail_bwd_pool", g_out, nhwc(g_pooled), None, y2, m2, r2, g2, b2, s, ms, rs, gs, bs, gy2, gs_t, a_t, b2_t,
@@ -913,6 +909,12 @@ def _tickets(n: int, like: torch.Tensor):
     return t
 
 
+def _fin_available(like: torch.Tensor) -> bool:
+    """May a launch made NOW on ``like``'s device finalise in the launch?  Depends on the phase (eager, a GraphedPhase capture, somebody else's
+    capture); asked through ``_tickets`` because the probe also makes the ring / the capture's chunk that the launches behind it draw from."""
+    return _tickets(0, like) is not None
+
+
 def _wu(w, transposed):
     """The prepared Winograd image of ``w`` for this form inside a ``wino_prepared`` scope (the `_pre` argument), else None."""
     return _WINO_ACTIVE.get((w.data_ptr(), transposed & 1)) if _WINO_ACTIVE else None
@@ -981,11 +983,18 @@ def _add_grad(p, g):
         p.grad = p.grad + g
 
 
-def _pair_wgrad(key, mine, ca, gamma, beta, slope, rows, h, w, ci, co, single, deliver):
-    """Park ``mine`` = (x, x2, gy, gs, mean, rstd, n) under ``key`` and return None, or -- when the other pass is parked there --
-    launch the paired weight gradient over both sets and return gw [rows][ci][co] (flat).  ``single(set)``: the one-set launch
-    (flat result; used when the library refuses the pair at the partner's batch size, and by ``pair_flush`` for a set that never
-    met a partner, whose result goes to ``deliver``)."""
+class WgradSet(NamedTuple):
+    """One pass' operands of a fused block's 3x3 weight-gradient launch -- exactly what a parked entry keeps alive.  x2: the second part of a
+    virtual cat; gs: the shortcut's output gradient (conv1 + shortcut in one launch); (mean, rstd) of x: normalised while staging (conv2 on y1)."""
+    x: torch.Tensor; x2: Optional[torch.Tensor]; gy: torch.Tensor; gs: Optional[torch.Tensor]                     # noqa: E702
+    mean: Optional[torch.Tensor]; rstd: Optional[torch.Tensor]; n: int                                            # noqa: E702
+
+
+def _pair_wgrad(key, mine: WgradSet, launch, single, deliver):
+    """Park ``mine`` under ``key`` and return None, or -- when the other pass is parked there -- launch the paired weight gradient over both
+    sets and return gw [rows][ci][co] (flat).  ``launch``: what both sets share, (rows, ca, gamma, beta, slope, (h, w, ci, co)).  ``single(set)``:
+    the one-set launch (flat: where the library refuses the pair at the partner's batch size; for ``pair_flush``, which hands it to ``deliver``)."""
+    rows, ca, gamma, beta, slope, dims = launch
     lst = _PAIR_STASH.get(key)
     if not lst:
         _PAIR_STASH.setdefault(key, []).append((mine, single, deliver))
@@ -993,16 +1002,370 @@ def _pair_wgrad(key, mine, ca, gamma, beta, slope, rows, h, w, ci, co, single, d
     other = lst.pop()[0]
     if not lst:
         del _PAIR_STASH[key]
-    xa, x2a, gya, gsa, ma, ra, na = mine
-    xb, x2b, gyb, gsb, mb, rb, nb = other
-    cat, aff, sc = int(x2a is not None), int(ma is not None), int(gsa is not None)
-    if not H.call("smsut_conv2d_wgrad_pair_supported", na, nb, h, w, ci, co, cat, aff, sc):
+    cat, aff, sc = int(mine.x2 is not None), int(mine.mean is not None), int(mine.gs is not None)
+    if not H.call("smsut_conv2d_wgrad_pair_supported", mine.n, other.n, *dims, cat, aff, sc):
         return single(mine) + single(other)
-    gw = torch.empty(rows * ci * co, dtype=torch.float32, device=xa.device)
-    ws = _ws(H.call("smsut_conv2d_wgrad_pair_ws", na, nb, h, w, ci, co, cat, aff, sc), xa)
-    H.call("smsut_conv2d_wgrad_pair", xa, x2a, gya, gsa, ma, ra, na, xb, x2b, gyb, gsb, mb, rb, nb, ca, gamma if aff else None,
-           beta if aff else None, float(slope), gw, ws, h, w, ci, co, _s())
+    gw = torch.empty(rows * dims[2] * dims[3], dtype=torch.float32, device=mine.x.device)
+    ws = _ws(H.call("smsut_conv2d_wgrad_pair_ws", mine.n, other.n, *dims, cat, aff, sc), mine.x)
+    H.call("smsut_conv2d_wgrad_pair", *mine, *other, ca, gamma if aff else None, beta if aff else None, float(slope), gw, ws, *dims, _s())
     return gw
+
+
+class BlockPlan(NamedTuple):
+    """What one fused BasicBlock launches: decided once, at the top of ``BasicBlockFn.forward`` (``_block_plan``), launched by the ``_bb_*``
+    stages, carried to the backward as ``ctx.plan``.  Shapes and forms only, no tensors.  DESIGN.md 4b lists what sets each field and what
+    each stage launches for it; cat: (ca, cb) of a block whose input is cat([xa, xb], 1); t3 / t3b: statistics tiles of conv1 / conv2."""
+    n: int; h: int; w: int; ci: int; co: int                                                                      # noqa: E702
+    cat: Optional[tuple]; has_sc: bool; virtual: bool; pool: bool; slope: float                                   # noqa: E702
+    f16a: bool; f16: bool; hs: bool; fused_sc: bool; fin: bool; inaff: bool; pair: bool                           # noqa: E702
+    t3: int; t3b: int                                                                                             # noqa: E702
+
+
+def _block_plan(like, cat, virtual, co, has_sc, slope, pool) -> BlockPlan:
+    n, ci, h, w = like.shape
+    ci, vc = (cat[0] + cat[1], 1) if virtual else (ci, 0)
+    # fp16 operands (config 5): both 3x3 convs of the block and their gradients, when every reduction is whole 16-channel chunks; same tile
+    # selection / statistics layout as the fp32 forms  (per conv: the 8 -> 16 first block keeps conv1 in fp32 -- half of a 16-channel chunk
+    # would be padding -- but its 16 -> 16 conv2 qualifies)
+    f16a = CONV_F16 and ci % 16 == 0 and co % 16 == 0
+    f16 = CONV_F16 and co % 16 == 0
+    t3 = H.call("smsut_conv2d_mfma_tiles", n, h, w, ci, co, 3, int(f16a))    # tile shape depends on (N, H, W, Cin, Cout, dtype)
+    t3b = H.call("smsut_conv2d_mfma_tiles", n, h, w, co, co, 3, int(f16))
+    # conv1 and the 1x1 shortcut read the same block input: one pass (the shortcut is conv1's centre tap with its own weights)
+    fused_sc = has_sc and bool(H.call("smsut_conv2d_fwd_sc_f16_supported" if f16a else "smsut_conv2d_fwd_sc_supported", n, h, w, ci, co, vc))
+    # fp16 operands: the block-internal raw conv outputs y1, y2, s never leave the block -- stored as fp16 (half the HBM bytes
+    # of every pass over them: conv epilogues, IN apply, both tail passes, the BST mask read), arithmetic on them in fp32
+    # (the 8 -> 16 first block: conv1 stays on fp32 operands -- the 8-channel form has no fp16 twin -- and stores fp16 all the same)
+    hs = ((f16a or ci == 8) and f16 and fused_sc and bool(H.call("smsut_conv2d_f16_hs_supported", n, h, w, ci, co, vc))
+          and bool(H.call("smsut_conv2d_f16_hs_supported", n, h, w, co, co, 0)))
+    # conv2 / wgrad2 normalise y1 while staging, for blocks of whole 16-channel tiles (r04: the register-row weight gradient takes
+    # the transform for +3 us at 16 -> 16 @256^2; the LDS-staged 16-channel kernel paid +55 us, which kept the 16-channel blocks
+    # out until then: uganConsis -1.0 %, U-Net -1.0 %)
+    inaff = not f16 and co % 16 == 0 and bool(H.call("smsut_conv2d_mfma_persistent", n, h, w, co, co, 3, 0))
+    # in-launch finalize of all three statistics sets of the block (fp32, fused shortcut, conv2 on the raw y1: the forms whose
+    # kernels carry it) -- decided once, so that the block never mixes the two ways for one statistics set
+    fin = fused_sc and not (f16a or hs) and inaff and _fin_available(like)
+    return BlockPlan(n, h, w, ci, co, cat, has_sc, virtual, pool, slope, f16a, f16, hs, fused_sc, fin, inaff, _PAIR_FWD and not CONV_F16, t3, t3b)
+
+
+def _bb_conv1(p: BlockPlan, x, x2, w1, ws, st):
+    """conv1 (+ the 1x1 shortcut: ``fused_sc``) with statistics from the epilogue; (x, x2): the parts of a virtual cat, else (x, None)."""
+    n, h, w, ci, co = p[:5]
+    act_dt = torch.float16 if p.hs else torch.float32
+    s = ps = ms = rs = None
+    p1 = _ws(n * p.t3 * co * 2, x)
+    y1 = new_act(n, co, h, w, x, act_dt)
+    if p.fused_sc:
+        s, ps = new_act(n, co, h, w, x, act_dt), _ws(n * p.t3 * co * 2, x)
+    m1, r1 = _vec(x, n, co), _vec(x, n, co)
+    if p.hs:
+        H.call("smsut_conv2d_fwd_mfma_stats_sc_f16_hs", x, x2, w1, ws, y1, s, p1, ps, n, h, w, ci, co, st)
+    elif p.fin:
+        # statistics of y1 AND of the shortcut finalised inside the launch (no smsut_in_finalize_* behind it)
+        ms, rs = _vec(x, n, co), _vec(x, n, co)
+        H.call("smsut_conv2d_fwd_mfma_stats_sc_fin", x, x2, w1, ws, y1, s, p1, ps, _tickets(n, x), m1, r1, ms, rs, IN_EPS,
+               n, h, w, ci, co, _wu(w1, 0), st)
+    elif p.fused_sc:
+        _conv3("smsut_conv2d_fwd_mfma_stats_sc_f16" if p.f16a else "smsut_conv2d_fwd_mfma_stats_sc", w1, 0, x, x2, w1, ws, y1, s,
+               p1, ps, n, h, w, ci, co, st)
+    elif p.virtual:
+        _conv3("smsut_conv2d_fwd_mfma_stats_cat_f16" if p.f16a else "smsut_conv2d_fwd_mfma_stats_cat", w1, 0, x, x2, w1, y1, p1, n, h, w, ci, co, st)
+    else:
+        _conv3("smsut_conv2d_fwd_mfma_stats_f16" if p.f16a else "smsut_conv2d_fwd_mfma_stats", w1, 0, x, w1, y1, p1, n, h, w, ci, co, 3, st)
+    return y1, p1, m1, r1, s, ps, ms, rs
+
+
+def _bb_conv2(p: BlockPlan, y1, p1, m1, r1, g1, b1, w2, ps, ms, rs, st):
+    """conv2 on act(IN1(y1)), normalised while staging (``inaff``, ``hs``) or applied into a1 first; then the statistics still due."""
+    n, h, w, _, co = p[:5]
+    hw, slope, a1 = h * w, p.slope, None
+    y2 = new_act(n, co, h, w, y1, torch.float16 if p.hs else torch.float32)
+    p2 = _ws(n * p.t3b * co * 2, y1)
+    if p.fin:                                            # (m2, r2 -- like m1, r1, ms, rs -- written by the conv launch itself)
+        m2, r2 = _vec(y1, n, co), _vec(y1, n, co)
+        H.call("smsut_conv2d_fwd_mfma_stats_inaff_fin", y1, w2, y2, p2, m1, r1, g1, b1, slope, _tickets(n, y1), m2, r2, IN_EPS,
+               n, h, w, co, co, _wu(w2, 0), st)
+    elif p.inaff:
+        # conv2 (and later its weight gradient) normalise the raw conv1 output while staging their tiles: a1 is never built
+        H.call("smsut_in_finalize_fwd", p1, p.t3, m1, r1, n, hw, co, IN_EPS, st)
+        _conv3("smsut_conv2d_fwd_mfma_stats_inaff", w2, 0, y1, w2, y2, p2, m1, r1, g1, b1, slope, n, h, w, co, co, st)
+    elif p.hs:
+        # conv2 (and later its weight gradient) widen the raw fp16 y1, normalise + activate and round it while staging: the
+        # operand bits smsut_instnorm_fwd_partials_hs2 would have stored -- a1 and the pass that writes it disappear
+        H.call("smsut_in_finalize_fwd", p1, p.t3, m1, r1, n, hw, co, IN_EPS, st)
+        H.call("smsut_conv2d_fwd_mfma_stats_inaff_f16_hsx", y1, w2, y2, p2, m1, r1, g1, b1, slope, n, h, w, co, co, st)
+    else:
+        a1 = new_act(n, co, h, w, y1)
+        H.call("smsut_instnorm_fwd_partials", y1, g1, b1, a1, m1, r1, p1, p.t3, n, hw, co, IN_EPS, slope, 1, st)
+        _conv3("smsut_conv2d_fwd_mfma_stats_f16" if p.f16 else "smsut_conv2d_fwd_mfma_stats", w2, 0, a1, w2, y2, p2, n, h, w, co, co, 3, st)
+    if not p.fin:
+        m2, r2 = _vec(y1, n, co), _vec(y1, n, co)
+        if p.fused_sc:
+            ms, rs = _vec(y1, n, co), _vec(y1, n, co)    # both sets are due now: ONE launch of the latency-bound finalize
+            H.call("smsut_in_finalize_fwd2", p2, p.t3b, m2, r2, ps, p.t3, ms, rs, n, hw, co, IN_EPS, st)
+        else:
+            H.call("smsut_in_finalize_fwd", p2, p.t3b, m2, r2, n, hw, co, IN_EPS, st)
+    return y2, a1, m2, r2, ms, rs
+
+
+def _bb_shortcut(p: BlockPlan, x, x2, ws, st):
+    """The 1x1 shortcut as a launch of its own (no fused form for the shape) and its statistics."""
+    n, h, w, ci, co = p[:5]
+    hw, s = h * w, new_act(n, co, h, w, x)
+    t1s = H.call("smsut_conv1x1_tiles", n, hw, co) if H.call("smsut_conv1x1_supported", ci, co) else 0     # the streaming 1x1 kernel's
+    t1 = t1s if (t1s or p.virtual) else H.call("smsut_conv2d_mfma_tiles", n, h, w, ci, co, 1, 0)   # (virtual: basic_block_cat_fusable saw t1s > 0)
+    ps = _ws(n * t1 * co * 2, x)
+    if p.virtual:
+        H.call("smsut_conv1x1_fwd_cat", x, x2, p.cat[0], ws, s, ps, n, hw, ci, co, st)
+    elif t1s:
+        H.call("smsut_conv1x1_fwd", x, ws, s, ps, n, hw, ci, co, 0, st)
+    else:
+        H.call("smsut_conv2d_fwd_mfma_stats", x, ws, s, ps, n, h, w, ci, co, 1, st)
+    ms, rs = _vec(x, n, co), _vec(x, n, co)
+    H.call("smsut_in_finalize_fwd", ps, t1, ms, rs, n, hw, co, IN_EPS, st)
+    return s, ms, rs
+
+
+def _bb_tail(p: BlockPlan, y2, m2, r2, g2, b2, s, ms, rs, gs, bs, st):
+    """IN2, the shortcut's IN, the residual add and the activation in one pass (+ the level's max-pool).  -> out, pooled, pool_idx"""
+    n, h, w, _, co = p[:5]
+    out, pooled, idx = new_act(n, co, h, w, y2), None, None
+    if p.pool:
+        pooled = new_act(n, co, h // 2, w // 2, y2)
+        idx = torch.empty(n * (h // 2) * (w // 2) * co, dtype=torch.uint8, device=y2.device)
+        H.call("smsut_restail_fwd_pool", y2, m2, r2, g2, b2, s, ms, rs, gs, bs, out, pooled, idx, n, h, w, co, p.slope, int(p.hs), st)
+    else:
+        H.call("smsut_restail_fwd_hs" if p.hs else "smsut_restail_fwd", y2, m2, r2, g2, b2, s, ms, rs, gs, bs, out, n, h * w, co, p.slope, st)
+    return out, pooled, idx
+
+
+class BlockBwd(NamedTuple):
+    """The backward's own decisions (``_block_bwd_plan``, at the top of ``BasicBlockFn.backward``)."""
+    chunks: int                           # partial-sum chunks of the InstanceNorm-backward reductions
+    nb: int; amax1: bool                  # amax handover: slots per tensor of [gy2 | gs_t | gy1], 0 = none / max |gy1| comes too       # noqa: E702
+    tail: str; fin_ok: bool               # "pool" | "hs" | "amax" | "fin" | "plain" / the tail's backward may finalise in its launch   # noqa: E702
+    pers2: bool; fin_b: bool              # conv2's data-gradient emits the IN-backward partial sums / and finalises them       # noqa: E702
+    f16w1: bool; f16w2: bool              # fp16-operand weight gradient of conv1 / conv2                             # noqa: E702
+    pair1: bool; pair2: bool              # the weight gradient of conv1 + shortcut / conv2 goes through ``_pair_wgrad``   # noqa: E702
+    fused_wsc16: bool; fused_wsc: bool    # conv1's and the shortcut's weight gradients in one pass over x: fp16 / any operands  # noqa: E702
+    fused_dsc16: bool                     # their data-gradients in one pass on fp16 operands (asked for: it decides the scale)
+    dx: Optional[str]                     # block-input gradient: None (not wanted) | "sc_f16" | "sc" | "split" | "accum" | "accum_k1"
+
+
+def _block_bwd_plan(p: BlockPlan, needs, mp, fin_available) -> BlockBwd:
+    """``mp``: both outputs of a pool block bring a gradient; ``fin_available()``: the finalize probe of THIS phase (the forward may
+    have run in another), asked at most once and only where a launch could use it."""
+    n, h, w, ci, co = p[:5]
+    f16a, f16, hs, has_sc, cat = p.f16a, p.f16, p.hs, p.has_sc, p.cat is not None
+    chunks = H.call("smsut_in_chunks", n, h * w, co)
+    # fp16 operands: the kernels that write gy2 / gs_t / gy1 hand their absolute maxima over (one slot per workgroup:
+    # [gy2 | gs_t | gy1], nb each), the scales of the gradient operands come from those slots instead of a pass over each tensor
+    nb = H.call("smsut_amax_blocks", n, h * w, co) if (f16 or f16a) and AMAX_HANDOVER else 0
+    fin_ok = not hs and not nb and (mp or has_sc) and fin_available()
+    tail = "pool" if mp else "hs" if hs else "amax" if nb else "fin" if fin_ok else "plain"
+    pers2 = bool(H.call("smsut_conv2d_mfma_persistent", n, h, w, co, co, 3, int(f16)))
+    fin_b = pers2 and p.fin and fin_ok                   # (p.fin: fp32 operands, conv shortcut -- so the probe above was made)
+    amax1 = pers2 and nb > 0 and (hs or f16a)
+    f16w2 = f16 and bool(H.call("smsut_conv2d_wgrad_f16_supported", n, h, w, co, co))
+    f16w1 = f16a and bool(H.call("smsut_conv2d_wgrad_f16_supported", n, h, w, ci, co))
+    # (p.pair: fp32 operands -- no hs, no f16w*, no fused_wsc16 -- so the pair queries are asked where the fp32 launches are due)
+    pair2 = p.pair and bool(H.call("smsut_conv2d_wgrad_pair_supported", n, n, h, w, co, co, 0, int(p.inaff), 0))
+    split_c = p.cat[0] if cat else 0
+    fused_wsc16 = has_sc and f16w1 and bool(H.call("smsut_conv2d_wgrad_sc_f16_supported", n, h, w, ci, co))
+    fused_dsc16 = (has_sc and f16a and (needs[0] or needs[11] or needs[12])
+                   and bool(H.call("smsut_conv2d_dgrad_sc_f16_supported", n, h, w, co, ci, split_c)))
+    fused_wsc = fused_wsc16 or (has_sc and not f16w1 and bool(H.call("smsut_conv2d_wgrad_sc_supported", n, h, w, ci, co)))
+    pair1 = p.pair and fused_wsc and bool(H.call("smsut_conv2d_wgrad_pair_supported", n, n, h, w, ci, co, int(p.virtual), 0, 1))
+    dx = None
+    if (needs[11] or needs[12]) if cat else needs[0]:
+        if fused_dsc16:
+            dx = "sc_f16"
+        elif has_sc and not f16a and H.call("smsut_conv2d_dgrad_sc_supported", n, h, w, co, ci, split_c):
+            dx = "sc"
+        elif (cat and has_sc and split_c % 16 == 0 and H.call("smsut_conv1x1_supported", co, ci)
+                and H.call("smsut_conv2d_mfma_split_supported", n, h, w, co, ci, split_c)):
+            dx = "split"
+        else:
+            dx = "accum" if not has_sc or H.call("smsut_conv1x1_supported", co, ci) else "accum_k1"    # (the shortcut's: streaming 1x1 | MFMA k = 1)
+    return BlockBwd(chunks, nb, amax1, tail, fin_ok, pers2, fin_b, f16w1, f16w2, pair1, pair2, fused_wsc16, fused_wsc, fused_dsc16, dx)
+
+
+def _bb_tail_bwd(p: BlockPlan, b: BlockBwd, g_out, g_pooled, pool_idx, out, y2, m2, r2, g2, b2, s, ms, rs, gs, bs, st):
+    """Residual tail: gradients of both raw conv outputs (or of the identity) in one reduce + one apply pass."""
+    n, h, w, _, co = p[:5]
+    hw, slope = h * w, p.slope
+    gy2, gs_t = new_act(n, co, h, w, y2), new_act(n, co, h, w, y2)
+    a_t, b2_t, bs_t = _vec(y2, n, co), _vec(y2, n, co), _vec(y2, n, co)
+    gg2, gb2 = _vec(y2, co), _vec(y2, co)
+    ggs, gbs = (_vec(y2, co), _vec(y2, co)) if p.has_sc else (None, None)
+    amax = _vec(y2, 3 * b.nb) if b.nb else None
+    tk = _tickets(n, y2) if b.tail == "pool" and b.fin_ok else None
+    io = (y2, m2, r2, g2, b2, s, ms, rs, gs, bs, gy2, gs_t, a_t, b2_t, bs_t, gg2, gb2, ggs, gbs, _ws(n * b.chunks * co * 3, y2))
+    if b.tail == "pool":
+        H.call("smsut_restail_bwd_pool", g_out, g_pooled, pool_idx, *io, tk, amax, n, h, w, co, slope, int(p.hs), st)
+    elif b.tail in ("hs", "amax"):
+        H.call("smsut_restail_bwd_hs" if p.hs else "smsut_restail_bwd_amax", g_out, out, *io, amax, n, hw, co, slope, st)
+    elif b.tail == "fin":
+        # the per-image means of the tail's backward finalised inside the partial-sum launch (two launches instead of three)
+        H.call("smsut_restail_bwd_fin", g_out, out, *io, _tickets(n, y2), n, hw, co, slope, st)
+    else:
+        H.call("smsut_restail_bwd", g_out, out, *io, n, hw, co, slope, st)
+    return gy2, gs_t, gg2, gb2, ggs, gbs, amax
+
+
+def _bb_dgrad2(p: BlockPlan, b: BlockBwd, gy2, w2, y1, m1, r1, g1, b1, amax, st):
+    """conv2's data-gradient + IN1 / LeakyReLU backward (mask recomputed from y1).  -> gy1, gg1, gb1, sc2 (the scale of gy2)"""
+    n, h, w, _, co = p[:5]
+    hw, slope, f16, hs, nb = h * w, p.slope, p.f16, p.hs, b.nb
+    ga1, gy1 = new_act(n, co, h, w, gy2), new_act(n, co, h, w, gy2)
+    a1m, b1m, gg1, gb1 = _vec(gy2, n, co), _vec(gy2, n, co), _vec(gy2, co), _vec(gy2, co)
+    sc2 = (_grad_scale_from(amax[:nb]) if amax is not None else _grad_scale(gy2)) if f16 else None   # serves conv2's data- and weight-gradient
+    if not b.pers2:
+        if f16:
+            H.call("smsut_conv2d_fwd_mfma_f16", gy2, w2, ga1, sc2, n, h, w, co, co, 3, 1, st)
+        else:
+            _conv3("smsut_conv2d_fwd_mfma", w2, 1, gy2, w2, ga1, n, h, w, co, co, 3, 1, st)
+        H.call("smsut_instnorm_bwd", ga1, y1, b1, m1, r1, g1, gy1, a1m, b1m, gg1, gb1, _ws(n * b.chunks * co * 3, gy2), n, hw, co, slope, st)
+        return gy1, gg1, gb1, sc2
+    # the dgrad epilogue masks its result and emits the InstanceNorm-backward partial sums: no reduction pass
+    pb = _ws(n * p.t3b * co * 2, gy2)                    # (the tiles of conv2's forward: same shape, same operand dtype)
+    if f16:
+        H.call("smsut_conv2d_dgrad_mfma_bwdstats_f16_hs" if hs else "smsut_conv2d_dgrad_mfma_bwdstats_f16", gy2, w2, ga1, pb, y1, m1, r1, g1, b1,
+               sc2, slope, n, h, w, co, co, st)
+    elif b.fin_b:                                        # in-launch finalize of the backward pair: a1m, b1m written by the launch itself
+        H.call("smsut_conv2d_dgrad_mfma_bwdstats_fin", gy2, w2, ga1, pb, y1, m1, r1, g1, b1, slope, _tickets(n, gy2), a1m, b1m,
+               n, h, w, co, co, _wu(w2, 1), st)
+    else:
+        _conv3("smsut_conv2d_dgrad_mfma_bwdstats", w2, 1, gy2, w2, ga1, pb, y1, m1, r1, g1, b1, slope, n, h, w, co, co, st)
+    if not b.fin_b:
+        H.call("smsut_in_finalize_bwd", pb, p.t3b, a1m, b1m, n, hw, co, st)
+    if hs or b.amax1:
+        H.call("smsut_in_apply_bwd_hs" if hs else "smsut_in_apply_bwd_amax", ga1, y1, m1, r1, g1, a1m, b1m, gy1, gg1, gb1,
+               amax[2 * nb:] if b.amax1 else None, n, hw, co, st)
+    else:
+        H.call("smsut_in_apply_bwd", ga1, y1, m1, r1, g1, a1m, b1m, gy1, gg1, gb1, n, hw, co, st)
+    return gy1, gg1, gb1, sc2
+
+
+def _bb_wgrad2(p: BlockPlan, b: BlockBwd, pair_w, y1, a1, gy2, w2, sc2, m1, r1, g1, b1, st):
+    """conv2's weight gradient; None when the operands were parked for the other generator pass (``_pair_wgrad``)."""
+    (n, h, w, _, co), slope = p[:5], p.slope
+    if p.hs or b.f16w2:
+        gw2 = new_weight(co, co, 3, 3, device=gy2.device)
+        wws = _ws(H.call("smsut_conv2d_wgrad_f16_ws", n, h, w, co, co), gy2)
+        if p.hs:
+            H.call("smsut_conv2d_wgrad_f16_xh_inaff", y1, gy2, gw2, wws, sc2, m1, r1, g1, b1, slope, n, h, w, co, co, st)
+        else:
+            H.call("smsut_conv2d_wgrad_f16", a1, None, 0, gy2, gw2, wws, sc2, n, h, w, co, co, st)
+        return gw2
+
+    def single2(t):                                      # -> flat [9][co][co]
+        g = _vec(t.x, 9 * co * co)
+        wws2 = _ws(H.call("smsut_conv2d_wgrad_mfma_ws", t.n, h, w, co, co, 3), t.x)
+        if t.mean is not None:
+            H.call("smsut_conv2d_wgrad_mfma_inaff", t.x, t.gy, g, wws2, t.mean, t.rstd, g1, b1, slope, t.n, h, w, co, co, _s())
+        else:
+            H.call("smsut_conv2d_wgrad_mfma", t.x, t.gy, g, wws2, t.n, h, w, co, co, 3, _s())
+        return g
+    as_w2 = lambda g: torch.as_strided(g, (co, co, 3, 3), hwio_strides(co, co, 3, 3))     # noqa: E731
+    mine2 = WgradSet(y1, None, gy2, None, m1, r1, n) if p.inaff else WgradSet(a1, None, gy2, None, None, None, n)
+    if not b.pair2:
+        return as_w2(single2(mine2))
+    # the other generator pass through this layer is (or will be) parked under the weight's storage: one launch for both
+    leaf2 = pair_w[1]
+    gw2 = _pair_wgrad(("w2", w2.data_ptr()), mine2, (9, 0, g1, b1, slope, (h, w, co, co)), single2, lambda g: _add_grad(leaf2, as_w2(g)))
+    return None if gw2 is None else as_w2(gw2)
+
+
+def _bb_wgrad1(p: BlockPlan, b: BlockBwd, pair_w, x, x2, gy1, gs_t, w1, amax, st):
+    """Weight gradients of conv1 and of the shortcut; (x, x2, ca): the parts of a virtual cat, else (x, None, 0).  -> gw1, gws (None,
+    None when the operands were parked for the other generator pass), sc1 (fp16 operands: the scale of conv1's gradient operand)"""
+    n, h, w, ci, co = p[:5]
+    hw, ca = h * w, (p.cat[0] if p.virtual else 0)
+    as_w1 = lambda g: torch.as_strided(g, (co, ci, 3, 3), hwio_strides(co, ci, 3, 3))                     # noqa: E731
+    as_ws = lambda g: torch.as_strided(g, (co, ci, 1, 1), hwio_strides(co, ci, 1, 1), 9 * ci * co)        # noqa: E731
+    # fp16 operands: the fused-shortcut kernels read [gy1 | gs_t] as ONE operand -> one scale over both tensors
+    if not p.f16a:
+        sc1 = None
+    elif b.fused_wsc16 or b.fused_dsc16:
+        sc1 = _grad_scale_from(amax[b.nb:]) if b.amax1 else _grad_scale2(gy1, gs_t)
+    else:
+        sc1 = _grad_scale_from(amax[2 * b.nb:]) if b.amax1 else _grad_scale(gy1)
+    # fused: both weight gradients in one pass over x: rows 0..8 = conv1's taps, row 9 = the 1x1 shortcut's
+    if b.fused_wsc16:
+        g10 = _vec(x, 10 * ci * co)
+        H.call("smsut_conv2d_wgrad_sc_f16", x, x2, ca, gy1, gs_t, g10, _ws(H.call("smsut_conv2d_wgrad_sc_f16_ws", n, h, w, ci, co), x),
+               sc1, n, h, w, ci, co, st)
+        return as_w1(g10), as_ws(g10), sc1
+    if b.fused_wsc:
+        def single1(t):                                  # -> flat [10][ci][co]
+            g = _vec(t.x, 10 * ci * co)
+            H.call("smsut_conv2d_wgrad_mfma_sc", t.x, t.x2, ca, t.gy, t.gs, g,
+                   _ws(H.call("smsut_conv2d_wgrad_sc_ws", t.n, h, w, ci, co), t.x), t.n, h, w, ci, co, _s())
+            return g
+        mine1 = WgradSet(x, x2, gy1, gs_t, None, None, n)
+        if b.pair1:
+            leaf1, leafs = pair_w[0], pair_w[2]
+            g10 = _pair_wgrad(("w1", w1.data_ptr()), mine1, (10, ca, None, None, p.slope, (h, w, ci, co)), single1,
+                              lambda g: (_add_grad(leaf1, as_w1(g)), _add_grad(leafs, as_ws(g))))
+        else:
+            g10 = single1(mine1)
+        return (None, None, sc1) if g10 is None else (as_w1(g10), as_ws(g10), sc1)     # (None: parked for the other pass / pair_flush)
+    gw1 = new_weight(co, ci, 3, 3, device=x.device)
+    wws = _ws(H.call("smsut_conv2d_wgrad_f16_ws", n, h, w, ci, co) if b.f16w1 else H.call("smsut_conv2d_wgrad_mfma_ws", n, h, w, ci, co, 3), x)
+    if b.f16w1:
+        H.call("smsut_conv2d_wgrad_f16", x, x2, ca, gy1, gw1, wws, sc1, n, h, w, ci, co, st)
+    elif p.virtual:
+        H.call("smsut_conv2d_wgrad_mfma_cat", x, x2, ca, gy1, gw1, wws, n, h, w, ci, co, 3, st)
+    else:
+        H.call("smsut_conv2d_wgrad_mfma", x, gy1, gw1, wws, n, h, w, ci, co, 3, st)
+    if not p.has_sc:
+        return gw1, None, sc1
+    gws = new_weight(co, ci, 1, 1, device=x.device)
+    wws1 = _ws(H.call("smsut_conv1x1_wgrad_ws", n, hw, ci, co), x)
+    if p.virtual:
+        H.call("smsut_conv1x1_wgrad_cat", x, x2, ca, gs_t, gws, wws1, n, hw, ci, co, st)
+    else:
+        H.call("smsut_conv1x1_wgrad", x, gs_t, gws, wws1, n, hw, ci, co, st)
+    return gw1, gws, sc1
+
+
+def _bb_dgrad1(p: BlockPlan, b: BlockBwd, gy1, gs_t, w1, ws, sc1, st):
+    """Block-input gradient (conv1's data-gradient + the shortcut's, the identity's being gs_t itself) into the parts (ga, gb) of a cat or into
+    gx.  ONE ladder for both: fused fp16, fused fp32, (cat) split 1x1 + split 3x3 on top, shortcut first + the 3x3 accumulating on top."""
+    n, h, w, ci, co = p[:5]
+    hw, split = h * w, p.cat is not None
+    ca, cb = p.cat if split else (0, 0)
+    ga, gb = (new_act(n, ca, h, w, gy1), new_act(n, cb, h, w, gy1)) if split else (None, None)
+    gx = None if (split and b.dx[:5] != "accum") else new_act(n, ci, h, w, gy1) if p.has_sc else gs_t
+    d0, d1 = (ga, gb) if split else (gx, None)           # where the fused forms write
+    if b.dx == "sc_f16":
+        H.call("smsut_conv2d_dgrad_mfma_sc_f16", gy1, gs_t, w1, ws, d0, d1, sc1, ca, n, h, w, co, ci, st)
+    elif b.dx == "sc":
+        # conv1's and the shortcut's data-gradients in ONE pass (the shortcut's is the centre tap of a second
+        # reduction half), written straight into the destination: no 1x1 kernel, no accumulate pass
+        H.call("smsut_conv2d_dgrad_mfma_sc", gy1, gs_t, w1, ws, d0, d1, ca, n, h, w, co, ci, st)
+    elif b.dx == "split":
+        # shortcut gradient first, the 3x3 data-gradient accumulates on top -- both straight into (ga, gb)
+        H.call("smsut_conv1x1_fwd_split", gs_t, ws, ga, gb, ca, n, hw, co, ci, 1, st)
+        if p.f16a:
+            H.call("smsut_conv2d_fwd_mfma_split_f16", gy1, w1, ga, gb, sc1, ca, n, h, w, co, ci, 3, st)
+        else:
+            _conv3("smsut_conv2d_fwd_mfma_split", w1, 1, gy1, w1, ga, gb, ca, n, h, w, co, ci, 3, st)
+    else:
+        # the shortcut's gradient lands in gx first; the 3x3 data-gradient then accumulates into it in its store
+        # epilogue (transposed | 2), which replaces a separate 3-pass add
+        if b.dx == "accum_k1":
+            H.call("smsut_conv2d_fwd_mfma", gs_t, ws, gx, n, h, w, co, ci, 1, 1, st)
+        elif p.has_sc:
+            H.call("smsut_conv1x1_fwd", gs_t, ws, gx, None, n, hw, co, ci, 1, st)
+        if p.f16a:
+            H.call("smsut_conv2d_fwd_mfma_f16", gy1, w1, gx, sc1, n, h, w, co, ci, 3, 3, st)
+        else:
+            _conv3("smsut_conv2d_fwd_mfma", w1, 1, gy1, w1, gx, n, h, w, co, ci, 3, 3, st)
+        if split:
+            H.call("smsut_concat2", ga, ca, gb, cb, gx, n * hw, 1, st)
+    return (None, ga, gb) if split else (gx, None, None)
 
 
 class BasicBlockFn(Function):
@@ -1024,408 +1387,45 @@ class BasicBlockFn(Function):
         # x None (with xa, xb): the cat is never materialised -- conv1, the shortcut and their weight gradients read the two
         # parts in place (virtual-cat entry points; chunk order and arithmetic of the materialised cat: same bits)
         leaves = (w1, w2, ws)                        # (as passed: the tensors autograd accumulates into)
-        ctx.cat_split = (xa.shape[1], xb.shape[1]) if xa is not None else None
-        virtual = x is None
-        ctx.virtual = virtual
-        if virtual:
-            xa, xb = nhwc(xa), nhwc(xb)
-            x = xa                                   # device / allocation hints below
-        w1, w2 = hwio(w1), hwio(w2)
-        x = nhwc(x)
-        has_sc = ws is not None
-        if has_sc:
-            ws = hwio(ws)
-        n, ci, h, w = x.shape
-        if virtual:
-            ci = xa.shape[1] + xb.shape[1]
-        co = w1.shape[0]
-        hw = h * w
+        cat = (xa.shape[1], xb.shape[1]) if xa is not None else None
+        x, x2 = (nhwc(xa), nhwc(xb)) if x is None else (nhwc(x), None)
+        w1, w2, ws = hwio(w1), hwio(w2), (hwio(ws) if ws is not None else None)
+        p = ctx.plan = _block_plan(x, cat, x2 is not None, w1.shape[0], ws is not None, float(slope), bool(pool))
         st = _s()
-        dev = x.device
-        slope = float(slope)
-
-        def stat(c):
-            return torch.empty(n, c, dtype=torch.float32, device=dev), torch.empty(n, c, dtype=torch.float32, device=dev)
-
-        # fp16 operands (config 5): both 3x3 convs of the block and their gradients, when every reduction is whole 16-channel
-        # chunks; same tile selection / statistics layout as the fp32 forms
-        # (per conv: the 8 -> 16 first block keeps conv1 in fp32 -- half of a 16-channel chunk would be padding -- but its
-        #  16 -> 16 conv2 qualifies)
-        f16a = CONV_F16 and ci % 16 == 0 and co % 16 == 0          # conv1 and its gradients
-        f16 = CONV_F16 and co % 16 == 0                            # conv2 and its gradients
-        ctx.f16 = (f16a, f16)
-        t3 = H.call("smsut_conv2d_mfma_tiles", n, h, w, ci, co, 3, int(f16a))    # tile shape depends on (N, H, W, Cin, Cout, dtype)
-        t3b = H.call("smsut_conv2d_mfma_tiles", n, h, w, co, co, 3, int(f16))
-        p1 = _ws(n * t3 * co * 2, x)
-        # conv1 and the 1x1 shortcut read the same block input: one pass (the shortcut is conv1's centre tap with its own weights)
-        fused_sc = has_sc and bool(H.call("smsut_conv2d_fwd_sc_f16_supported" if f16a else "smsut_conv2d_fwd_sc_supported",
-                                          n, h, w, ci, co, 1 if virtual else 0))
-        # fp16 operands: the block-internal raw conv outputs y1, y2, s never leave the block -- stored as fp16 (half the HBM bytes
-        # of every pass over them: conv epilogues, IN apply, both tail passes, the BST mask read), arithmetic on them in fp32
-        # (the 8 -> 16 first block: conv1 stays on fp32 operands -- the 8-channel form has no fp16 twin -- and stores fp16 all the same)
-        hs = ((f16a or ci == 8) and f16 and fused_sc
-              and bool(H.call("smsut_conv2d_f16_hs_supported", n, h, w, ci, co, 1 if virtual else 0))
-              and bool(H.call("smsut_conv2d_f16_hs_supported", n, h, w, co, co, 0)))
-        ctx.hs = hs
-        act_dt = torch.float16 if hs else torch.float32
-        # in-launch finalize of all three statistics sets of the block (fp32, fused shortcut, conv2 on the raw y1: the forms whose
-        # kernels carry it) -- decided once, so that the block never mixes the two ways for one statistics set
-        fin = (fused_sc and not (f16a or f16 or hs) and co % 16 == 0
-               and bool(H.call("smsut_conv2d_mfma_persistent", n, h, w, co, co, 3, 0)) and _tickets(0, x) is not None)
-        ctx.fin = fin
-        y1 = new_act(n, co, h, w, x, act_dt)
-        if fused_sc:
-            s = new_act(n, co, h, w, x, act_dt)
-            ps, t1 = _ws(n * t3 * co * 2, x), t3
-            if hs:
-                H.call("smsut_conv2d_fwd_mfma_stats_sc_f16_hs", xa if virtual else x, xb if virtual else None, w1, ws, y1, s, p1, ps,
-                       n, h, w, ci, co, st)
-            elif fin:
-                # statistics of y1 AND of the shortcut finalised inside the launch (no smsut_in_finalize_* behind it)
-                m1, r1 = stat(co)
-                ms, rs = stat(co)
-                H.call("smsut_conv2d_fwd_mfma_stats_sc_fin", xa if virtual else x, xb if virtual else None, w1, ws, y1, s, p1, ps,
-                       _tickets(n, x), m1, r1, ms, rs, IN_EPS, n, h, w, ci, co, _wu(w1, 0), st)
-            else:
-                _conv3("smsut_conv2d_fwd_mfma_stats_sc_f16" if f16a else "smsut_conv2d_fwd_mfma_stats_sc", w1, 0, xa if virtual else x,
-                       xb if virtual else None, w1, ws, y1, s, p1, ps, n, h, w, ci, co, st)
-        elif virtual:
-            _conv3("smsut_conv2d_fwd_mfma_stats_cat_f16" if f16a else "smsut_conv2d_fwd_mfma_stats_cat", w1, 0, xa, xb, w1, y1, p1, n, h, w,
-                   ci, co, st)
-        else:
-            _conv3("smsut_conv2d_fwd_mfma_stats_f16" if f16a else "smsut_conv2d_fwd_mfma_stats", w1, 0, x, w1, y1, p1, n, h, w, ci, co, 3, st)
-        if not fin:
-            m1, r1 = stat(co)
-        y2 = new_act(n, co, h, w, x, act_dt)
-        p2 = _ws(n * t3b * co * 2, x)
-        # conv2 / wgrad2 normalise y1 while staging, for blocks of whole 16-channel tiles (r04: the register-row weight gradient takes
-        # the transform for +3 us at 16 -> 16 @256^2; the LDS-staged 16-channel kernel paid +55 us, which kept the 16-channel blocks
-        # out until then: uganConsis -1.0 %, U-Net -1.0 %)
-        inaff = (not f16 and co % 16 == 0
-                 and bool(H.call("smsut_conv2d_mfma_persistent", n, h, w, co, co, 3, 0)))
-        ctx.inaff = inaff
-        if inaff and fin:
-            a1 = None
-            m2, r2 = stat(co)
-            H.call("smsut_conv2d_fwd_mfma_stats_inaff_fin", y1, w2, y2, p2, m1, r1, g1, b1, slope, _tickets(n, x), m2, r2, IN_EPS,
-                   n, h, w, co, co, _wu(w2, 0), st)
-        elif inaff:
-            # conv2 (and later its weight gradient) normalise the raw conv1 output while staging their tiles: a1 is never built
-            a1 = None
-            H.call("smsut_in_finalize_fwd", p1, t3, m1, r1, n, hw, co, IN_EPS, st)
-            _conv3("smsut_conv2d_fwd_mfma_stats_inaff", w2, 0, y1, w2, y2, p2, m1, r1, g1, b1, slope, n, h, w, co, co, st)
-        else:
-            if hs:
-                # conv2 (and later its weight gradient) widen the raw fp16 y1, normalise + activate and round it while staging: the
-                # operand bits smsut_instnorm_fwd_partials_hs2 would have stored -- a1 and the pass that writes it disappear
-                a1 = None
-                H.call("smsut_in_finalize_fwd", p1, t3, m1, r1, n, hw, co, IN_EPS, st)
-                H.call("smsut_conv2d_fwd_mfma_stats_inaff_f16_hsx", y1, w2, y2, p2, m1, r1, g1, b1, slope, n, h, w, co, co, st)
-            else:
-                a1 = new_act(n, co, h, w, x)
-                H.call("smsut_instnorm_fwd_partials", y1, g1, b1, a1, m1, r1, p1, t3, n, hw, co, IN_EPS, slope, 1, st)
-                _conv3("smsut_conv2d_fwd_mfma_stats_f16" if f16 else "smsut_conv2d_fwd_mfma_stats", w2, 0, a1, w2, y2, p2, n, h, w, co, co, 3, st)
-        if fin:
-            pass                                             # (m2, r2, ms, rs: written by the conv launches themselves)
-        else:
-            m2, r2 = stat(co)
-            if fused_sc:
-                ms, rs = stat(co)                            # both sets are due now: ONE launch of the latency-bound finalize
-                H.call("smsut_in_finalize_fwd2", p2, t3b, m2, r2, ps, t1, ms, rs, n, hw, co, IN_EPS, st)
-            else:
-                H.call("smsut_in_finalize_fwd", p2, t3b, m2, r2, n, hw, co, IN_EPS, st)
-        if fused_sc:
-            pass
-        elif has_sc:
-            s = new_act(n, co, h, w, x)
-            t1 = H.call("smsut_conv1x1_tiles", n, hw, co) if H.call("smsut_conv1x1_supported", ci, co) else 0
-            if virtual:                                      # (basic_block_cat_fusable checked t1 > 0)
-                ps = _ws(n * t1 * co * 2, x)
-                H.call("smsut_conv1x1_fwd_cat", xa, xb, xa.shape[1], ws, s, ps, n, hw, ci, co, st)
-            elif t1:
-                ps = _ws(n * t1 * co * 2, x)
-                H.call("smsut_conv1x1_fwd", x, ws, s, ps, n, hw, ci, co, 0, st)
-            else:
-                t1 = H.call("smsut_conv2d_mfma_tiles", n, h, w, ci, co, 1, 0)
-                ps = _ws(n * t1 * co * 2, x)
-                H.call("smsut_conv2d_fwd_mfma_stats", x, ws, s, ps, n, h, w, ci, co, 1, st)
-            ms, rs = stat(co)
-            H.call("smsut_in_finalize_fwd", ps, t1, ms, rs, n, hw, co, IN_EPS, st)
-        else:
-            s, ms, rs = x, None, None
-        out = new_act(n, co, h, w, x)
-        ctx.pool = bool(pool)
-        if pool:
-            pooled = new_act(n, co, h // 2, w // 2, x)
-            ctx.pool_idx = torch.empty(n * (h // 2) * (w // 2) * co, dtype=torch.uint8, device=dev)
-            H.call("smsut_restail_fwd_pool", y2, m2, r2, g2, b2, s, ms, rs, gs, bs, out, pooled, ctx.pool_idx, n, h, w, co, slope, int(hs), st)
-        else:
-            H.call("smsut_restail_fwd_hs" if hs else "smsut_restail_fwd", y2, m2, r2, g2, b2, s, ms, rs, gs, bs, out, n, hw, co, slope, st)
-        ctx.has_sc = has_sc
-        ctx.slope = slope
-        ctx.pair = _PAIR_FWD and not CONV_F16
-        ctx.pair_w = leaves if ctx.pair else None      # the leaves a parked set's gradient goes to if it never meets a partner
-        if virtual:
-            ctx.save_for_backward(xa, w1, w2, ws, y1, a1, y2, s, out, m1, r1, m2, r2, ms, rs, g1, b1, g2, gs, b2, bs, xb)
-        elif has_sc:
-            ctx.save_for_backward(x, w1, w2, ws, y1, a1, y2, s, out, m1, r1, m2, r2, ms, rs, g1, b1, g2, gs, b2, bs)
-        else:
-            ctx.save_for_backward(x, w1, w2, y1, a1, y2, out, m1, r1, m2, r2, g1, b1, g2)
+        y1, p1, m1, r1, s, ps, ms, rs = _bb_conv1(p, x, x2, w1, ws, st)
+        y2, a1, m2, r2, ms, rs = _bb_conv2(p, y1, p1, m1, r1, g1, b1, w2, ps, ms, rs, st)
+        if p.has_sc and not p.fused_sc:
+            s, ms, rs = _bb_shortcut(p, x, x2, ws, st)
+        out, pooled, ctx.pool_idx = _bb_tail(p, y2, m2, r2, g2, b2, s if p.has_sc else x, ms, rs, gs, bs, st)
+        ctx.pair_w = leaves if p.pair else None      # the leaves a parked set's gradient goes to if it never meets a partner
+        # ONE layout for the virtual-cat, conv-shortcut and identity forms: what a form lacks is None (identity: s is x itself)
+        ctx.save_for_backward(x, x2, w1, w2, ws, y1, a1, y2, s, out, m1, r1, m2, r2, ms, rs, g1, b1, g2,
+                              *((gs, b2, bs) if p.has_sc else (None, None, None)))
         return (out, pooled) if pool else out
 
     @staticmethod
     @once_differentiable
     def backward(ctx, g_out, g_pooled=None):
-        xb_part = None
-        if ctx.virtual:
-            x, w1, w2, ws, y1, a1, y2, s, out, m1, r1, m2, r2, ms, rs, g1, b1, g2, gs, b2, bs, xb_part = ctx.saved_tensors
-        elif ctx.has_sc:
-            x, w1, w2, ws, y1, a1, y2, s, out, m1, r1, m2, r2, ms, rs, g1, b1, g2, gs, b2, bs = ctx.saved_tensors
-        else:
-            x, w1, w2, y1, a1, y2, out, m1, r1, m2, r2, g1, b1, g2 = ctx.saved_tensors
-            ws = ms = rs = gs = b2 = bs = None
-            s = x
-        slope = ctx.slope
-        n, ci, h, w = x.shape
-        if ctx.pool and g_out is None:                   # (no skip gradient: the pooled path's alone, through the plain pooling backward)
-            g_out = new_act(n, w1.shape[0], h, w, x)
-            H.call("smsut_maxpool2_bwd", nhwc(g_pooled), out, g_out, n, h, w, w1.shape[0], _s())
+        p = ctx.plan
+        x, x2, w1, w2, ws, y1, a1, y2, s, out, m1, r1, m2, r2, ms, rs, g1, b1, g2, gs, b2, bs = ctx.saved_tensors
+        if p.pool and g_out is None:                     # (no skip gradient: the pooled path's alone, through the plain pooling backward)
+            g_out = new_act(p.n, p.co, p.h, p.w, x)
+            H.call("smsut_maxpool2_bwd", nhwc(g_pooled), out, g_out, p.n, p.h, p.w, p.co, _s())
             g_pooled = None
         g_out = nhwc(g_out)
-        mp = ctx.pool and g_pooled is not None           # two gradients: routed together inside the tail backward's loads
-        if mp:
-            g_pooled = nhwc(g_pooled)
-        if ctx.virtual:
-            ci = x.shape[1] + xb_part.shape[1]           # x is the first part here
-        co = w1.shape[0]
-        hw = h * w
+        mp = p.pool and g_pooled is not None             # two gradients: routed together inside the tail backward's loads
+        g_pooled = nhwc(g_pooled) if mp else None
+        b = _block_bwd_plan(p, ctx.needs_input_grad, mp, lambda: _fin_available(x))
         st = _s()
-        dev = x.device
-
-        def vec(*shape):
-            return torch.empty(*shape, dtype=torch.float32, device=dev)
-
-        chunks = H.call("smsut_in_chunks", n, hw, co)
-        # ---- residual tail: gradients of both raw conv outputs (or of the identity) in one reduce + one apply pass
-        gy2, gs_t = new_act(n, co, h, w, x), new_act(n, co, h, w, x)
-        a_t, b2_t, bs_t = vec(n, co), vec(n, co), vec(n, co)
-        gg2, gb2 = vec(co), vec(co)
-        ggs, gbs = (vec(co), vec(co)) if ctx.has_sc else (None, None)
-        f16a, f16 = ctx.f16                                  # fp16 operands for conv1 / conv2 and their gradients
-        # fp16 operands: the kernels that write gy2 / gs_t / gy1 hand their absolute maxima over (one slot per workgroup:
-        # [gy2 | gs_t | gy1], nb each), the scales of the gradient operands come from those slots instead of a pass over each tensor
-        nb = H.call("smsut_amax_blocks", n, hw, co) if (f16 or f16a) and AMAX_HANDOVER else 0
-        amax = torch.empty(3 * nb, dtype=torch.float32, device=dev) if nb else None
-        hs = ctx.hs
-        if mp:
-            tk = _tickets(n, x) if (not hs and amax is None and _tickets(0, x) is not None) else None
-            H.call("smsut_restail_bwd_pool", g_out, g_pooled, ctx.pool_idx, y2, m2, r2, g2, b2, s, ms, rs, gs, bs, gy2, gs_t, a_t, b2_t,
-                   bs_t, gg2, gb2, ggs, gbs, _ws(n * chunks * co * 3, x), tk, amax, n, h, w, co, slope, int(hs), st)
-        elif hs:
-            H.call("smsut_restail_bwd_hs", g_out, out, y2, m2, r2, g2, b2, s, ms, rs, gs, bs, gy2, gs_t, a_t, b2_t, bs_t, gg2, gb2,
-                   ggs, gbs, _ws(n * chunks * co * 3, x), amax, n, hw, co, slope, st)
-        elif amax is not None:
-            H.call("smsut_restail_bwd_amax", g_out, out, y2, m2, r2, g2, b2, s, ms, rs, gs, bs, gy2, gs_t, a_t, b2_t, bs_t, gg2, gb2,
-                   ggs, gbs, _ws(n * chunks * co * 3, x), amax, n, hw, co, slope, st)
-        elif ctx.has_sc and _tickets(0, x) is not None:
-            # the per-image means of the tail's backward finalised inside the partial-sum launch (two launches instead of three)
-            H.call("smsut_restail_bwd_fin", g_out, out, y2, m2, r2, g2, b2, s, ms, rs, gs, bs, gy2, gs_t, a_t, b2_t, bs_t, gg2, gb2,
-                   ggs, gbs, _ws(n * chunks * co * 3, x), _tickets(n, x), n, hw, co, slope, st)
-        else:
-            H.call("smsut_restail_bwd", g_out, out, y2, m2, r2, g2, b2, s, ms, rs, gs, bs, gy2, gs_t, a_t, b2_t, bs_t, gg2, gb2,
-                   ggs, gbs, _ws(n * chunks * co * 3, x), n, hw, co, slope, st)
+        gy2, gs_t, gg2, gb2, ggs, gbs, amax = _bb_tail_bwd(p, b, g_out, g_pooled, ctx.pool_idx, out, y2, m2, r2, g2, b2,
+                                                           s if p.has_sc else x, ms, rs, gs, bs, st)    # (identity: s is x itself)
         # (forking the three weight-gradient launches to a second stream inside this node was measured 1-3 % SLOWER
         #  than the single-stream order below -- profiles/r01_notes.md)
-        # ---- conv2 data-gradient + IN1 / LeakyReLU backward (mask recomputed from y1)
-        ga1 = new_act(n, co, h, w, x)
-        gy1 = new_act(n, co, h, w, x)
-        a1m, b1m, gg1, gb1 = vec(n, co), vec(n, co), vec(co), vec(co)
-        sc2 = (_grad_scale_from(amax[:nb]) if amax is not None else _grad_scale(gy2)) if f16 else None   # serves conv2's data- and weight-gradient
-        amax1 = False                                        # amax[2] = max |gy1| written
-        if H.call("smsut_conv2d_mfma_persistent", n, h, w, co, co, 3, int(f16)):
-            # the dgrad epilogue masks its result and emits the InstanceNorm-backward partial sums: no reduction pass
-            tb = H.call("smsut_conv2d_mfma_tiles", n, h, w, co, co, 3, int(f16))
-            pb = _ws(n * tb * co * 2, x)
-            fin_b = ctx.fin and not (hs or f16) and _tickets(0, x) is not None      # in-launch finalize of the backward pair
-            if hs:
-                H.call("smsut_conv2d_dgrad_mfma_bwdstats_f16_hs", gy2, w2, ga1, pb, y1, m1, r1, g1, b1, sc2, slope, n, h, w, co, co, st)
-            elif f16:
-                H.call("smsut_conv2d_dgrad_mfma_bwdstats_f16", gy2, w2, ga1, pb, y1, m1, r1, g1, b1, sc2, slope, n, h, w, co, co, st)
-            elif fin_b:
-                H.call("smsut_conv2d_dgrad_mfma_bwdstats_fin", gy2, w2, ga1, pb, y1, m1, r1, g1, b1, slope, _tickets(n, x), a1m, b1m,
-                       n, h, w, co, co, _wu(w2, 1), st)
-            else:
-                _conv3("smsut_conv2d_dgrad_mfma_bwdstats", w2, 1, gy2, w2, ga1, pb, y1, m1, r1, g1, b1, slope, n, h, w, co, co, st)
-            if not fin_b:                                    # (else: a1m, b1m written by the data-gradient launch itself)
-                H.call("smsut_in_finalize_bwd", pb, tb, a1m, b1m, n, hw, co, st)
-            if hs:
-                H.call("smsut_in_apply_bwd_hs", ga1, y1, m1, r1, g1, a1m, b1m, gy1, gg1, gb1, amax[2 * nb:] if amax is not None else None,
-                       n, hw, co, st)
-                amax1 = amax is not None
-            elif amax is not None and f16a:
-                H.call("smsut_in_apply_bwd_amax", ga1, y1, m1, r1, g1, a1m, b1m, gy1, gg1, gb1, amax[2 * nb:], n, hw, co, st)
-                amax1 = True
-            else:
-                H.call("smsut_in_apply_bwd", ga1, y1, m1, r1, g1, a1m, b1m, gy1, gg1, gb1, n, hw, co, st)
-        else:
-            if f16:
-                H.call("smsut_conv2d_fwd_mfma_f16", gy2, w2, ga1, sc2, n, h, w, co, co, 3, 1, st)
-            else:
-                _conv3("smsut_conv2d_fwd_mfma", w2, 1, gy2, w2, ga1, n, h, w, co, co, 3, 1, st)
-            H.call("smsut_instnorm_bwd", ga1, y1, b1, m1, r1, g1, gy1, a1m, b1m, gg1, gb1, _ws(n * chunks * co * 3, x),
-                   n, hw, co, slope, st)
-        f16w2 = f16 and bool(H.call("smsut_conv2d_wgrad_f16_supported", n, h, w, co, co))
-        f16w1 = f16a and bool(H.call("smsut_conv2d_wgrad_f16_supported", n, h, w, ci, co))
-        gw2 = new_weight(co, co, 3, 3, device=dev) if (hs or f16w2) else None
-        if hs:
-            H.call("smsut_conv2d_wgrad_f16_xh_inaff", y1, gy2, gw2, _ws(H.call("smsut_conv2d_wgrad_f16_ws", n, h, w, co, co), x), sc2,
-                   m1, r1, g1, b1, slope, n, h, w, co, co, st)
-        elif f16w2:
-            H.call("smsut_conv2d_wgrad_f16", a1, None, 0, gy2, gw2, _ws(H.call("smsut_conv2d_wgrad_f16_ws", n, h, w, co, co), x),
-                   sc2, n, h, w, co, co, st)
-        else:
-            def single2(t):                               # -> flat [9][co][co]
-                g = torch.empty(9 * co * co, dtype=torch.float32, device=dev)
-                wws2 = _ws(H.call("smsut_conv2d_wgrad_mfma_ws", t[6], h, w, co, co, 3), t[0])
-                if t[4] is not None:
-                    H.call("smsut_conv2d_wgrad_mfma_inaff", t[0], t[2], g, wws2, t[4], t[5], g1, b1, slope, t[6], h, w, co, co, _s())
-                else:
-                    H.call("smsut_conv2d_wgrad_mfma", t[0], t[2], g, wws2, t[6], h, w, co, co, 3, _s())
-                return g
-            as_w2 = lambda g: torch.as_strided(g, (co, co, 3, 3), hwio_strides(co, co, 3, 3))     # noqa: E731
-            mine2 = (y1, None, gy2, None, m1, r1, n) if ctx.inaff else (a1, None, gy2, None, None, None, n)
-            if ctx.pair and H.call("smsut_conv2d_wgrad_pair_supported", n, n, h, w, co, co, 0, int(ctx.inaff), 0):
-                # the other generator pass through this layer is (or will be) parked under the weight's storage: one launch for both
-                leaf2 = ctx.pair_w[1]
-                gw2 = _pair_wgrad(("w2", w2.data_ptr()), mine2, 0, g1, b1, slope, 9, h, w, co, co, single2,
-                                  lambda g: _add_grad(leaf2, as_w2(g)))
-                if gw2 is not None:
-                    gw2 = as_w2(gw2)
-            else:
-                gw2 = as_w2(single2(mine2))
-        # ---- conv1 and the shortcut
-        split_c = ctx.cat_split[0] if ctx.cat_split is not None else 0
-        fused_wsc16 = ctx.has_sc and f16w1 and bool(H.call("smsut_conv2d_wgrad_sc_f16_supported", n, h, w, ci, co))
-        fused_dsc16 = (ctx.has_sc and f16a and (ctx.needs_input_grad[0] or ctx.needs_input_grad[11] or ctx.needs_input_grad[12])
-                       and bool(H.call("smsut_conv2d_dgrad_sc_f16_supported", n, h, w, co, ci, split_c)))
-        # fp16 operands: the fused-shortcut kernels read [gy1 | gs_t] as ONE operand -> one scale over both tensors
-        if not f16a:
-            sc1 = None
-        elif fused_wsc16 or fused_dsc16:
-            sc1 = _grad_scale_from(amax[nb:]) if amax1 else _grad_scale2(gy1, gs_t)
-        else:
-            sc1 = _grad_scale_from(amax[2 * nb:]) if amax1 else _grad_scale(gy1)
-        fused_wsc = fused_wsc16 or (ctx.has_sc and not f16w1 and bool(H.call("smsut_conv2d_wgrad_sc_supported", n, h, w, ci, co)))
-        if fused_wsc:
-            # both weight gradients in one pass over x: rows 0..8 = conv1's taps, row 9 = the 1x1 shortcut's
-            if fused_wsc16:
-                g10 = torch.empty(10 * ci * co, dtype=torch.float32, device=dev)
-                gw1 = torch.as_strided(g10, (co, ci, 3, 3), hwio_strides(co, ci, 3, 3))
-                gws = torch.as_strided(g10, (co, ci, 1, 1), hwio_strides(co, ci, 1, 1), 9 * ci * co)
-                H.call("smsut_conv2d_wgrad_sc_f16", x, xb_part if ctx.virtual else None, x.shape[1] if ctx.virtual else 0, gy1, gs_t,
-                       g10, _ws(H.call("smsut_conv2d_wgrad_sc_f16_ws", n, h, w, ci, co), x), sc1, n, h, w, ci, co, st)
-            else:
-                ca1 = x.shape[1] if ctx.virtual else 0
-
-                def single1(t):                           # -> flat [10][ci][co]
-                    g = torch.empty(10 * ci * co, dtype=torch.float32, device=dev)
-                    H.call("smsut_conv2d_wgrad_mfma_sc", t[0], t[1], ca1, t[2], t[3], g,
-                           _ws(H.call("smsut_conv2d_wgrad_sc_ws", t[6], h, w, ci, co), t[0]), t[6], h, w, ci, co, _s())
-                    return g
-                as_w1 = lambda g: torch.as_strided(g, (co, ci, 3, 3), hwio_strides(co, ci, 3, 3))                     # noqa: E731
-                as_ws = lambda g: torch.as_strided(g, (co, ci, 1, 1), hwio_strides(co, ci, 1, 1), 9 * ci * co)        # noqa: E731
-                mine1 = (x, xb_part if ctx.virtual else None, gy1, gs_t, None, None, n)
-                if ctx.pair and H.call("smsut_conv2d_wgrad_pair_supported", n, n, h, w, ci, co, int(ctx.virtual), 0, 1):
-                    leaf1, leafs = ctx.pair_w[0], ctx.pair_w[2]
-                    g10 = _pair_wgrad(("w1", w1.data_ptr()), mine1, ca1, None, None, slope, 10, h, w, ci, co, single1,
-                                      lambda g: (_add_grad(leaf1, as_w1(g)), _add_grad(leafs, as_ws(g))))
-                else:
-                    g10 = single1(mine1)
-                if g10 is None:                              # parked: the other pass returns the sum (or pair_flush delivers it)
-                    gw1 = gws = None
-                else:
-                    gw1, gws = as_w1(g10), as_ws(g10)
-        else:
-            gw1 = new_weight(co, ci, 3, 3, device=dev)
-        if fused_wsc:
-            pass
-        elif f16w1:
-            wws = _ws(H.call("smsut_conv2d_wgrad_f16_ws", n, h, w, ci, co), x)
-            if ctx.virtual:
-                H.call("smsut_conv2d_wgrad_f16", x, xb_part, x.shape[1], gy1, gw1, wws, sc1, n, h, w, ci, co, st)
-            else:
-                H.call("smsut_conv2d_wgrad_f16", x, None, 0, gy1, gw1, wws, sc1, n, h, w, ci, co, st)
-        else:
-            wws = _ws(H.call("smsut_conv2d_wgrad_mfma_ws", n, h, w, ci, co, 3), x)
-            if ctx.virtual:
-                H.call("smsut_conv2d_wgrad_mfma_cat", x, xb_part, x.shape[1], gy1, gw1, wws, n, h, w, ci, co, 3, st)
-            else:
-                H.call("smsut_conv2d_wgrad_mfma", x, gy1, gw1, wws, n, h, w, ci, co, 3, st)
-        if not fused_wsc:
-            gws = None
-        if ctx.has_sc and not fused_wsc:
-            gws = new_weight(co, ci, 1, 1, device=dev)
-            wws1 = _ws(H.call("smsut_conv1x1_wgrad_ws", n, hw, ci, co), x)
-            if ctx.virtual:
-                H.call("smsut_conv1x1_wgrad_cat", x, xb_part, x.shape[1], gs_t, gws, wws1, n, hw, ci, co, st)
-            else:
-                H.call("smsut_conv1x1_wgrad", x, gs_t, gws, wws1, n, hw, ci, co, st)
-        gx = None
-        if ctx.cat_split is not None:
-            ga = gb = None
-            if ctx.needs_input_grad[11] or ctx.needs_input_grad[12]:
-                ca, cb = ctx.cat_split
-                ga, gb = new_act(n, ca, h, w, x), new_act(n, cb, h, w, x)
-                if fused_dsc16:
-                    H.call("smsut_conv2d_dgrad_mfma_sc_f16", gy1, gs_t, w1, ws, ga, gb, sc1, ca, n, h, w, co, ci, st)
-                elif ctx.has_sc and not f16a and H.call("smsut_conv2d_dgrad_sc_supported", n, h, w, co, ci, ca):
-                    # conv1's and the shortcut's data-gradients in ONE pass (the shortcut's is the centre tap of a second
-                    # reduction half), written straight into (ga, gb): no 1x1 kernel, no accumulate pass
-                    H.call("smsut_conv2d_dgrad_mfma_sc", gy1, gs_t, w1, ws, ga, gb, ca, n, h, w, co, ci, st)
-                elif (ctx.has_sc and ca % 16 == 0 and H.call("smsut_conv1x1_supported", co, ci)
-                        and H.call("smsut_conv2d_mfma_split_supported", n, h, w, co, ci, ca)):
-                    # shortcut gradient first, the 3x3 data-gradient accumulates on top -- both straight into (ga, gb)
-                    H.call("smsut_conv1x1_fwd_split", gs_t, ws, ga, gb, ca, n, hw, co, ci, 1, st)
-                    if f16a:
-                        H.call("smsut_conv2d_fwd_mfma_split_f16", gy1, w1, ga, gb, sc1, ca, n, h, w, co, ci, 3, st)
-                    else:
-                        _conv3("smsut_conv2d_fwd_mfma_split", w1, 1, gy1, w1, ga, gb, ca, n, h, w, co, ci, 3, st)
-                else:
-                    gx = new_act(n, ci, h, w, x)
-                    if H.call("smsut_conv1x1_supported", co, ci):
-                        H.call("smsut_conv1x1_fwd", gs_t, ws, gx, None, n, hw, co, ci, 1, st)
-                    else:
-                        H.call("smsut_conv2d_fwd_mfma", gs_t, ws, gx, n, h, w, co, ci, 1, 1, st)
-                    if f16a:
-                        H.call("smsut_conv2d_fwd_mfma_f16", gy1, w1, gx, sc1, n, h, w, co, ci, 3, 3, st)
-                    else:
-                        _conv3("smsut_conv2d_fwd_mfma", w1, 1, gy1, w1, gx, n, h, w, co, ci, 3, 3, st)
-                    H.call("smsut_concat2", ga, ca, gb, cb, gx, n * hw, 1, st)
-            return None, gw1, gg1, gb1, gw2, gg2, gb2, gws, ggs, gbs, None, ga, gb, None
-        if ctx.needs_input_grad[0]:
-            # the shortcut's gradient lands in gx first; the 3x3 data-gradient then accumulates into it in its store
-            # epilogue (transposed | 2), which replaces a separate 3-pass add
-            if fused_dsc16:
-                gx = new_act(n, ci, h, w, x)
-                H.call("smsut_conv2d_dgrad_mfma_sc_f16", gy1, gs_t, w1, ws, gx, None, sc1, 0, n, h, w, co, ci, st)
-                return gx, gw1, gg1, gb1, gw2, gg2, gb2, gws, ggs, gbs, None, None, None, None
-            if ctx.has_sc and not f16a and H.call("smsut_conv2d_dgrad_sc_supported", n, h, w, co, ci, 0):
-                gx = new_act(n, ci, h, w, x)
-                H.call("smsut_conv2d_dgrad_mfma_sc", gy1, gs_t, w1, ws, gx, None, 0, n, h, w, co, ci, st)
-                return gx, gw1, gg1, gb1, gw2, gg2, gb2, gws, ggs, gbs, None, None, None, None
-            if ctx.has_sc:
-                gx = new_act(n, ci, h, w, x)
-                if H.call("smsut_conv1x1_supported", co, ci):
-                    H.call("smsut_conv1x1_fwd", gs_t, ws, gx, None, n, hw, co, ci, 1, st)
-                else:
-                    H.call("smsut_conv2d_fwd_mfma", gs_t, ws, gx, n, h, w, co, ci, 1, 1, st)
-            else:
-                gx = gs_t
-            if f16a:
-                H.call("smsut_conv2d_fwd_mfma_f16", gy1, w1, gx, sc1, n, h, w, co, ci, 3, 3, st)
-            else:
-                _conv3("smsut_conv2d_fwd_mfma", w1, 1, gy1, w1, gx, n, h, w, co, ci, 3, 3, st)
-        return gx, gw1, gg1, gb1, gw2, gg2, gb2, gws, ggs, gbs, None, None, None, None
+        gy1, gg1, gb1, sc2 = _bb_dgrad2(p, b, gy2, w2, y1, m1, r1, g1, b1, amax, st)
+        gw2 = _bb_wgrad2(p, b, ctx.pair_w, y1, a1, gy2, w2, sc2, m1, r1, g1, b1, st)
+        gw1, gws, sc1 = _bb_wgrad1(p, b, ctx.pair_w, x, x2, gy1, gs_t, w1, amax, st)
+        gx, ga, gb = _bb_dgrad1(p, b, gy1, gs_t, w1, ws, sc1, st) if b.dx else (None, None, None)
+        return gx, gw1, gg1, gb1, gw2, gg2, gb2, gws, ggs, gbs, None, ga, gb, None
 
 
 class CatParts:
