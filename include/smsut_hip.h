@@ -496,6 +496,22 @@ int smsut_warp_joint(const float* img, const int64_t* msk, const float* aff, con
    point on the first / last pixel; image and label map sampled at (y + dy, x + dx) with order 0, constant 0 outside. */
 int smsut_elastic_deform(const float* img, const int64_t* msk, const float* coef, float* oimg, int64_t* omsk, int N, int H,
                          int W, int P, void* stream);
+/* Photometric augmentation (reference data_loader/baseLoader.py:102-109: ColorJitter(0.4, 0.4, 0.4, 0.125), then
+ * RandomGammaCorrection, on mode-L 8-bit slices; saturation and hue are the identity there).  img / out: [N][HW] fp32, img on the
+ * [0, 1] scale; a pixel is first quantised to the level PIL would hold, floor(x * 255 + 0.5) clamped to 0..255.  Per slice the chain
+ * brightness = blend(0, v, b), contrast = blend(m, v, c) (m = int(mean + 0.5) of the slice as it is when that step runs; blend =
+ * PIL's ImagingBlend: fp32 multiply, fp32 add, truncation, clipped when the factor leaves [0, 1]) and the gamma table collapses into
+ * one 256-entry table built from the slice's histogram; the output is out_tab[final level] (out_tab: 256 floats chosen by the
+ * caller -- level / 255, or the normalised values).  Bit-reproducible (integer adds, fixed-order fp32); pinned to Pillow's outputs.
+ *   smsut_photo_parts(HW) = G, the histogram kernel's workgroups per slice (at most 16).
+ *   smsut_photo_hist: part [N][G][256] int32, every row written by its own workgroup (no zeroing needed), summed by the next call.
+ *   smsut_photo_apply: params [N][4] = {order (0: brightness first, 1: contrast first), b, c, gamma drawn (0 / 1)};
+ *     part == NULL: no jitter (gamma only, no histogram launch needed); gtab: uint8 [N][256] gamma tables, read for the slices whose
+ *     flag is set, NULL: no gamma.  out must not alias img.  N <= 65535. */
+int smsut_photo_parts(int HW);
+int smsut_photo_hist(const float* img, int* part, int N, int HW, void* stream);
+int smsut_photo_apply(const float* img, const int* part /*nullable*/, const float* params, const uint8_t* gtab /*nullable*/,
+                      const float* out_tab, float* out, int N, int HW, void* stream);
 int smsut_bilinear2_fwd(const float* x, float* y, int N, int H, int W, int C, void* stream);
 int smsut_bilinear2_bwd(const float* gy, float* gx, int N, int H, int W, int C, void* stream);
 /* networks.py building blocks of ResnetGenerator / NLayerDiscriminator: reflection / replication /

@@ -183,6 +183,10 @@ SIGNATURES: Dict[str, str] = {
     "smsut_copy_channels": "p ii p ii i l s",
     "smsut_concat2": "p i p i p l i s",
     "smsut_modal_planes": "ppp i l ii s",
+    # photometric.hip
+    "smsut_photo_parts": "i",
+    "smsut_photo_hist": "pp ii s",
+    "smsut_photo_apply": "pppppp ii s",
     # loss.hip
     "smsut_dicece_ws": "i l ii",
     "smsut_dicece_stats": "ppppp i l ii s",
@@ -232,7 +236,8 @@ _NO_STATUS = _RET_I64 | {"smsut_conv2d_k4_supported", "smsut_conv2d_f16_supporte
                          "smsut_conv2d_fwd_sc_supported", "smsut_conv2d_fwd_sc_f16_supported", "smsut_conv2d_dgrad_sc_supported",
                          "smsut_conv2d_dgrad_sc_f16_supported", "smsut_conv2d_wgrad_sc_f16_supported", "smsut_conv2d_f16_hs_supported",
                          "smsut_conv2d_wgrad_sc_supported", "smsut_convT2x2_ps_supported", "smsut_conv2d_wgrad_pair_supported",
-                         "smsut_conv2d_wgrad_mfma_slabs", "smsut_conv2d_wgrad_pair_slabs", "smsut_conv2d_mfma_form", "smsut_sgd_chunk", "smsut_ema_chunk"}     # (return a count / a form id, not a status)
+                         "smsut_conv2d_wgrad_mfma_slabs", "smsut_conv2d_wgrad_pair_slabs", "smsut_conv2d_mfma_form", "smsut_sgd_chunk", "smsut_ema_chunk",
+                         "smsut_photo_parts"}     # (return a count / a form id, not a status)
 
 _CT = {"p": ctypes.c_void_p, "i": ctypes.c_int, "l": ctypes.c_int64, "f": ctypes.c_float, "d": ctypes.c_double,
        "s": ctypes.c_void_p}

@@ -16,6 +16,9 @@ Parameter draws follow the reference's distributions (uniform angle; torchvision
 with sigma ~ U(sigmas), applied with probability p).  ``elasticdeform`` is a third-party package that is not installed here (and
 not pinned by the reference): its published algorithm is restated (oracle/augment_oracle.py::elastic_deform_grid builds it from
 scipy.ndimage's spline routines, the code elasticdeform's C extension derives from); parity at that boundary is UNPINNED.
+
+The photometric half (``colorJitter`` / ``gammaCorrect``, baseLoader.py:102-109) follows the joint passes: ``GpuPhotometricAugment`` /
+``photometric`` below, two launches per batch (``csrc/photometric.hip``), pinned bit for bit to Pillow (tests/golden/photometric_pil.npz).
 """
 import math
 import random
@@ -197,3 +200,133 @@ def warp_joint(img, msk, aff, ctrl, Ho, Wo):
         omsk = torch.empty(n, Ho, Wo, dtype=torch.int64, device=dev)
     H.call("smsut_warp_joint", img, msk, aff, ctrl, oimg, omsk, n, H_, W_, Ho, Wo, P, H.stream_ptr())
     return oimg, omsk
+
+
+# ---- photometric augmentation: ColorJitter + RandomGammaCorrection (baseLoader.py:102-109, externalTransforms.py:23-43) --------------
+
+def gamma_table(gamma):
+    """torchvision's ``F.adjust_gamma`` for an 8-bit PIL image, gain 1: the 256-entry table ``int((255 + 1 - 1e-3) * (l / 255) **
+    gamma)`` built in float64 and applied with ``Image.point``.  torchvision is not installed here and the reference does not pin a
+    version: this is its published formula restated; parity at that boundary is UNPINNED.  -> uint8 [256]."""
+    g = float(gamma)
+    return np.array([min(255, int((255 + 1 - 1e-3) * (l / 255.0) ** g)) for l in range(256)], dtype=np.uint8)
+
+
+_OUT_TABS = {}
+
+
+def level_table(device, normalize):
+    """The 256 output values of the photometric pass, on ``device``.  ``normalize=False``: level / 255 (IEEE fp32 quotient, ToTensor's
+    scale).  ``normalize=True``: what the loader's own chain ``uint8 -> float().div_(255.0) -> sub_(0.5).div_(0.5)`` yields for every
+    level, computed ONCE by that chain on the device -- the normalised batch is then bit-identical to what the loader produces from
+    the same levels, by construction."""
+    key = (str(torch.device(device)), bool(normalize))
+    if key not in _OUT_TABS:
+        if normalize:
+            _OUT_TABS[key] = torch.arange(256, dtype=torch.uint8, device=device).float().div_(255.0).sub_(0.5).div_(0.5)
+        else:
+            _OUT_TABS[key] = torch.from_numpy(np.arange(256, dtype=np.float32) / np.float32(255.0)).to(device)
+    return _OUT_TABS[key]
+
+
+def photometric(img, jitter=None, gammas=None, normalize=False, out_tab=None):
+    """The photometric pass with explicit parameters.  img: fp32 on the device, [N,1,H,W] or [N,H,W], on the [0, 1] scale (first
+    quantised to the 8-bit level PIL would hold: floor(x * 255 + 0.5), clamped).
+
+    jitter: None, or per slice ``(order, b, c)`` -- order 0: brightness then contrast, 1: contrast then brightness; brightness =
+    PIL blend(0, v, b), contrast = blend(m, v, c) with m the rounded mean of the slice as it is at that step (``ImageEnhance``).
+    gammas: None, or per slice a gamma or None (not drawn).  Output: ``out_tab[level]`` -- level / 255, the Normalize(0.5, 0.5)
+    values with ``normalize=True``, or a caller's 256-float device table.  One launch, two with jitter (the histogram)."""
+    if not img.is_cuda:
+        raise H.SmsutHipError("the photometric pass runs on a HIP device (no CPU fallback in the product path)")
+    assert img.dtype == torch.float32 and (img.dim() == 3 or (img.dim() == 4 and img.shape[1] == 1)), "slices are single-channel fp32"
+    n, hw = int(img.shape[0]), int(img.shape[-1] * img.shape[-2])
+    dev = img.device
+    img = img.contiguous()
+    rows = np.zeros((n, 4), dtype=np.float32)
+    if jitter is not None:
+        assert len(jitter) == n
+        rows[:, :3] = np.asarray([(float(o), b, c) for (o, b, c) in jitter], dtype=np.float32).reshape(n, 3)
+    tabs = np.zeros((0, 256), dtype=np.uint8)
+    if gammas is not None and any(g is not None for g in gammas):
+        assert len(gammas) == n
+        ident = np.arange(256, dtype=np.uint8)
+        tabs = np.stack([ident if g is None else gamma_table(g) for g in gammas])
+        rows[:, 3] = [0.0 if g is None else 1.0 for g in gammas]
+    # parameter rows and gamma tables travel in ONE upload: [n * 16 bytes of fp32 rows | n * 256 bytes of tables]
+    buf = torch.from_numpy(np.concatenate([rows.view(np.uint8).ravel(), tabs.ravel()])).to(dev)
+    params = buf[:n * 16].view(torch.float32)
+    gtab = buf[n * 16:] if len(tabs) else None
+    if out_tab is None:
+        out_tab = level_table(dev, normalize)
+    assert out_tab.is_cuda and out_tab.dtype == torch.float32 and out_tab.numel() == 256 and out_tab.is_contiguous()
+    part = None
+    if jitter is not None:
+        part = level_histogram(img, _partials=True)
+    out = torch.empty_like(img)
+    H.call("smsut_photo_apply", img, part, params, gtab, out_tab, out, n, hw, H.stream_ptr())
+    return out
+
+
+def level_histogram(img, _partials=False):
+    """Histogram of the quantised 8-bit levels per slice (``smsut_photo_hist``): int32 [N, 256] -- the per-workgroup rows summed
+    (``_partials``: the rows themselves, [N, G, 256], as the apply kernel reads them)."""
+    if not img.is_cuda:
+        raise H.SmsutHipError("the photometric pass runs on a HIP device (no CPU fallback in the product path)")
+    n, hw = int(img.shape[0]), int(img.shape[-1] * img.shape[-2])
+    img = img.contiguous()
+    g = H.call("smsut_photo_parts", hw)
+    part = torch.empty(n, g, 256, dtype=torch.int32, device=img.device)
+    H.call("smsut_photo_hist", img, part, n, hw, H.stream_ptr())
+    return part if _partials else part.sum(1, dtype=torch.int32)
+
+
+class GpuPhotometricAugment:
+    """``colorJitter`` and ``gammaCorrect`` of ``config.data_aug`` as one device pass per batch.
+
+    ColorJitter(brightness=0.4, contrast=0.4, saturation=0.4, hue=0.125) is always applied when on; on the reference's mode-L slices
+    saturation (ImageEnhance.Color's degenerate image is the image itself) and hue (torchvision returns L images untouched) are the
+    identity, so a slice's jitter is b, c and which of the two comes first.  RandomGammaCorrection draws gamma, then a coin (p)."""
+    brightness = 0.4             # the reference hard-codes these (baseLoader.py:104)
+    contrast = 0.4
+    saturation = 0.4
+    hue = 0.125
+    gamma_p = 0.5
+
+    def __init__(self, data_aug):
+        self.cfg = dict(data_aug or {})
+        self.jitter = bool(self.cfg.get("colorJitter"))
+        self.gamma = bool(self.cfg.get("gammaCorrect"))
+        self.gammas = tuple(self.cfg.get("gammaCorrect_gammas", (0.7, 1.5)))
+
+    @property
+    def enabled(self):
+        return self.jitter or self.gamma
+
+    def draw(self, n):
+        """Per-sample parameters from the host ``random``, in the reference's order per sample: the four jitter factors (brightness,
+        contrast, saturation, hue: the last two are drawn because the reference draws them, and dropped) and the shuffle of the four
+        adjustments -- of which only whether brightness precedes contrast matters, a fair coin --, then gamma, then the gamma coin
+        (externalTransforms.py:35-38: drawn before the coin, like the elastic sigma).  -> (jitter, gammas) as ``photometric`` takes them."""
+        jit, gam = ([] if self.jitter else None), ([] if self.gamma else None)
+        for _ in range(n):
+            if self.jitter:
+                b = random.uniform(max(0.0, 1.0 - self.brightness), 1.0 + self.brightness)
+                c = random.uniform(max(0.0, 1.0 - self.contrast), 1.0 + self.contrast)
+                random.uniform(max(0.0, 1.0 - self.saturation), 1.0 + self.saturation)
+                random.uniform(-self.hue, self.hue)
+                order = [0, 1, 2, 3]
+                random.shuffle(order)
+                jit.append((0 if order.index(0) < order.index(1) else 1, b, c))
+            if self.gamma:
+                g = random.uniform(self.gammas[0], self.gammas[1])
+                gam.append(g if random.random() < self.gamma_p else None)
+        return jit, gam
+
+    def __call__(self, img, params=None, normalize=False):
+        """img [N,1,H,W] fp32 on the [0, 1] scale -> the augmented slices on that scale, or normalised to [-1, 1] (``normalize``: the
+        pass then stands in for the loader's Normalize(0.5, 0.5))."""
+        if not img.is_cuda:
+            raise H.SmsutHipError("the photometric pass runs on a HIP device (no CPU fallback in the product path)")
+        jit, gam = params if params is not None else self.draw(int(img.shape[0]))
+        return photometric(img, jit, gam, normalize=normalize)

@@ -1,6 +1,7 @@
 """Single-modality round-robin batch samplers and the PNG slice dataset of the reference's input pipeline
 (data_loader/inTurnLoader.py:15-97, data_loader/balanceLoader.py:17-69, baseLoader.py:87-112), with the joint
-geometric augmentation moved from PIL worker processes to ONE device kernel per batch (``gpu_augment.GpuJointAugment``).
+geometric augmentation moved from PIL worker processes to ONE device kernel per batch (``gpu_augment.GpuJointAugment``) and the
+photometric one (``colorJitter`` / ``gammaCorrect``) to a device pass after it (``gpu_augment.GpuPhotometricAugment``).
 
 Batch contract (what every trainer consumes): ``(img fp32 [B,1,H,W] in [-1,1], msk int64 [B,H,W], modality int64 [B],
 names list[str] 'm_pid_z')`` -- every batch holds slices of ONE modality, modalities taking turns.
@@ -17,7 +18,7 @@ import numpy as np
 import torch
 
 from .. import config as cfg
-from .gpu_augment import GpuJointAugment
+from .gpu_augment import GpuJointAugment, GpuPhotometricAugment
 
 
 class InTurnTrainBatchSampler:
@@ -137,10 +138,13 @@ class BalanceDataset:
 class InTurnLoader:
     """Iterable over batches: gathers the sampler's ids from the in-RAM uint8 arrays, uploads them (pinned, async),
     converts to the ToTensor + Normalize(0.5, 0.5) range on the device (baseLoader.py:89-90) and applies the joint
-    augmentation there."""
+    augmentation there; ``photometric`` (ColorJitter / RandomGammaCorrection, baseLoader.py:102-109) runs after it, on the 8-bit
+    levels, and writes the normalised values itself.  Its parameters are drawn per batch after the joint ones (the reference
+    interleaves the two per sample in its workers)."""
 
-    def __init__(self, dataset, batch_sampler, device, augment: GpuJointAugment = None):
+    def __init__(self, dataset, batch_sampler, device, augment: GpuJointAugment = None, photometric: GpuPhotometricAugment = None):
         self.ds, self.sampler, self.device, self.augment = dataset, batch_sampler, torch.device(device), augment
+        self.photometric = photometric if photometric is not None and photometric.enabled else None
 
     def __len__(self):
         return len(self.sampler)
@@ -163,7 +167,10 @@ class InTurnLoader:
             msk = msk8.to(torch.int64)
             if self.augment is not None:                                                  # joint augmentation BEFORE Normalize, as
                 img, msk = self.augment(img, msk)                                         # baseLoader.py:92-108 (fill = 0 = black)
-            img = img.sub_(0.5).div_(0.5)                                                 # Normalize(0.5, 0.5)
+            if self.photometric is not None:                                              # img transforms, Normalize included
+                img = self.photometric(img, normalize=True)
+            else:
+                img = img.sub_(0.5).div_(0.5)                                             # Normalize(0.5, 0.5)
             mdl = torch.tensor([self.ds.modality[i] for i in ids], dtype=torch.int64)
             yield img, msk, mdl, [self.ds.names[i] for i in ids]
 
@@ -175,7 +182,8 @@ def get_loader(data_root, phase, fold, batch_size, data_aug=None, load_in_ram: b
     if phase in ("train", "val"):
         sampler = InTurnTrainBatchSampler(ds.modal_sample_ids, batch_size, shuffle=False, rank=rank, world=world)
         aug = GpuJointAugment(data_aug, cfg.input_size) if data_aug else None
+        photo = GpuPhotometricAugment(data_aug) if data_aug else None
     else:
         sampler = InTurnTestBatchSampler(ds.modal_sample_ids, batch_size)
-        aug = None
-    return InTurnLoader(ds, sampler, device, aug)
+        aug = photo = None
+    return InTurnLoader(ds, sampler, device, aug, photo)
