@@ -253,10 +253,10 @@ def test_dice_ce(ops, batch_dice, n_cls):
     from oracle import smsut_oracle as O
     lg = (rnd(3, n_cls, 16, 16, seed=1) * 2).requires_grad_(True)
     lb = torch.from_numpy(np.random.RandomState(2).randint(0, n_cls, size=(3, 16, 16)).astype(np.int64))
-    ref = O.dice_ce(lg, lb, 0.5, 0.5, batch_dice)
+    ref = O.dice_ce(lg, lb, 0.3, 0.7, batch_dice)           # (CE weight, Dice weight) unequal: a swap of the two shows
     ref.backward()
     ld = dev(lg.detach()).requires_grad_(True)
-    out = ops.dice_ce(ld, dev(lb), 0.5, 0.5, batch_dice)
+    out = ops.dice_ce(ld, dev(lb), 0.3, 0.7, batch_dice)
     (out * 1.7).backward()                                  # a non-unit upstream gradient
     assert abs(out.item() - ref.item()) < 1e-6
     assert rel_err(ld.grad.cpu().numpy(), 1.7 * lg.grad.numpy()) < 1e-5
