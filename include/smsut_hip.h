@@ -109,7 +109,9 @@ int smsut_conv2d_wgrad_mfma(const float* x, const float* gy, float* gw, float* w
 
 /* 1x1 convolutions as streaming GEMMs (shortcuts blocks.py:63,95-97; up-path blocks.py:45; nn.Linear ugan.py:295): the
  * activation operand goes global -> registers (no LDS, no barrier in the loop), only the weights are staged.
- * transposed = 1 is the data-gradient.  stats (nullable): InstanceNorm partials [N][smsut_conv1x1_tiles][Ndim][2]. */
+ * transposed = 1 is the data-gradient.  stats (nullable): InstanceNorm partials [N][smsut_conv1x1_tiles][Ndim][2].
+ * The weight gradients (smsut_conv1x1_wgrad, smsut_conv1x1_wgrad_cat) take any Cin, Cout with (Cin * Cout) % 4 == 0 -- their
+ * split slabs are summed as float4s -- and refuse every other pair with an invalid-argument status before anything is launched. */
 int smsut_conv1x1_supported(int Kdim, int Ndim);
 int smsut_conv1x1_tiles(int N, int HW, int Ndim);
 int smsut_conv1x1_fwd(const float* x, const float* w, float* y, float* stats /*nullable*/, int N, int HW, int Kdim,
@@ -338,7 +340,9 @@ int64_t smsut_convT2x2_wgrad_mfma_ws(int N, int H, int W, int Cin, int Cout);
 int smsut_convT2x2_wgrad_mfma(const float* x, const float* gy, float* gw, float* workspace, int N, int H, int W, int Cin,
                               int Cout, void* stream);
 /* The same transposed conv through the 1x1 kernels' pixel-shuffle forms (x read once per 64-column slab of the 4 * Cout tap-major
- * columns instead of once per tap; Cout % 16 == 0): forward and weight gradient; the data gradient is already one pass. */
+ * columns instead of once per tap; Cout % 16 == 0): forward and weight gradient; the data gradient is already one pass.
+ * smsut_convT2x2_ps_supported: Cout == 16 and Cin <= 256 (the forward's weight image of one 64-column slab is 256 B per input
+ * channel and stays within 64 KiB of LDS); every other pair belongs to the per-tap kernels above. */
 int smsut_convT2x2_ps_supported(int Cin, int Cout);
 int smsut_convT2x2_fwd_ps(const float* x, const float* w, float* y, int N, int H, int W, int Cin, int Cout, void* stream);
 int64_t smsut_convT2x2_wgrad_ps_ws(int N, int H, int W, int Cin, int Cout);

@@ -465,7 +465,9 @@ int smsut_convT2x2_ps_supported(int Cin, int Cout) {
   // Cout == 16 only (the 128^2 -> 256^2 level): there the four taps are one 64-column slab -- 32x128^2 32->16: forward 66.4 ->
   // 62.1 us, weight gradient 91.4 -> 53.2 us; from 32 output channels on the per-tap MFMA kernels win (64->32: 38.6 / 42.2 and
   // 48.2 / 49.8 us; 128->64: 32.2 / 34.1 and 40.4 / 49.0) -- scratch/convt_probe.py.  The kernels take any Cout % 16 == 0.
-  return Cout == 16 && smsut_conv1x1_supported(Cin, 4 * Cout);
+  // Cin <= 256: the forward stages [Cin/16][4][64][4] floats of weights per 64-column workgroup, 64 KiB at 256 input channels
+  // (the launch asks for no more than the default dynamic LDS limit); wider inputs go to the per-tap MFMA kernels.
+  return Cout == 16 && Cin <= 256 && smsut_conv1x1_supported(Cin, 4 * Cout);
 }
 
 int smsut_convT2x2_fwd_ps(const float* x, const float* w, float* y, int N, int H, int W, int Cin, int Cout, void* stream) {
@@ -523,6 +525,7 @@ static int conv1x1_wgrad_launch(const float* x, const float* gy, float* gw, floa
                                 int Cout, void* stream, const float* x2, int ca) {
   SMSUT_REQUIRE(x && gy && gw && workspace && N > 0 && HW > 0 && Cin > 0 && Cout > 0);
   SMSUT_REQUIRE(!x2 || (ca > 0 && ca < Cin && ca % 16 == 0));
+  SMSUT_REQUIRE(((int64_t)Cin * Cout) % 4 == 0);     // sum_parts moves the [Cin][Cout] slabs as float4s
   const int64_t P = (int64_t)N * HW;
   const int cit = Cin > 16 ? 2 : 1, cot = Cout > 16 ? 2 : 1;
   const Plan1 p = plan_wgrad1(P, Cin, Cout, cit, cot);
