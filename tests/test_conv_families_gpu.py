@@ -14,21 +14,16 @@ doubles); outputs and workspaces are NaN inside and carry a sentinel guard behin
 its ``*_ws`` query; the ``*_supported`` predicate is asserted before a launch.  Bars are the ones ``test_ops_gpu.py`` holds these
 kernels to, on ``conftest.rel_err``: 1e-5 forward / data-gradient, 5e-5 weight gradient; each case prints its figure.  One test per
 family ties ``ops.conv2d`` / ``ops.conv_transpose2x2`` to the direct call bit for bit."""
-import numpy as np
 import pytest
 import torch
-import torch.nn.functional as F
 
-from conftest import rel_err
+from conv_edge_helpers import cdiv, check, conv_ref, gen, guarded_out, out_buf, poisoned, rn, untouched
 
 pytestmark = pytest.mark.gpu
 
 FWD_BAR = 1e-5
 WGRAD_BAR = 5e-5
-SENT = 12345.0
-GUARD = 256
 EW_CAP_ITEMS = 2048 * 256          # work items of one trip of a capped elementwise grid (ew_grid)
-NAN = float("nan")
 
 
 @pytest.fixture(scope="module")
@@ -45,61 +40,6 @@ def H():
     from smsut_amd import _hip
     assert torch.cuda.is_available(), "gpu tests need an MI355X"
     return _hip
-
-
-def poisoned(n_floats):
-    """n_floats of NaN (a partial that is read but never written shows) followed by a sentinel guard in the same allocation"""
-    buf = torch.full((int(n_floats) + GUARD,), float("nan"), device="cuda")
-    buf[int(n_floats):] = SENT
-    return buf, buf[int(n_floats):]
-
-
-def guarded_out(n):
-    buf = torch.full((n + GUARD,), SENT, device="cuda")
-    return buf, buf[n:]
-
-
-def untouched(*guards):
-    return all(bool((g == SENT).all()) for g in guards)
-
-
-def out_buf(*shape):
-    """an output tensor of NaN with the sentinel guard behind it: (tensor, guard)"""
-    n = int(np.prod(shape))
-    buf, guard = poisoned(n)
-    return buf[:n].view(*shape), guard
-
-
-def gen(seed):
-    return torch.Generator(device="cpu").manual_seed(seed)
-
-
-def rn(g, *shape, scale=1.0):
-    return torch.randn(*shape, generator=g) * scale
-
-
-def check(tag, got, ref, bar):
-    e = rel_err(got.detach().cpu().numpy(), ref.detach().numpy())
-    print(f"{tag}: rel_err {e:.3g} bar {bar:.3g}")
-    assert e < bar, tag
-
-
-def cdiv(a, b):
-    return (a + b - 1) // b
-
-
-def conv_ref(x, w, bias, stride, pad, gy=None):
-    """fp64 reference of a convolution on NHWC x and [KH][KW][Cin][Cout] w: y, and with gy also (gx, gw, gb), all in the kernels'
-    layouts"""
-    x64 = x.double().permute(0, 3, 1, 2).requires_grad_(True)
-    w64 = w.double().permute(3, 2, 0, 1).requires_grad_(True)
-    b64 = bias.double().requires_grad_(True) if bias is not None else None
-    y = F.conv2d(x64, w64, b64, stride=stride, padding=pad)
-    if gy is None:
-        return y.detach().permute(0, 2, 3, 1)
-    grads = torch.autograd.grad(y, [x64, w64] + ([b64] if bias is not None else []), gy.double().permute(0, 3, 1, 2))
-    return (y.detach().permute(0, 2, 3, 1), grads[0].permute(0, 2, 3, 1), grads[1].permute(2, 3, 1, 0),
-            grads[2] if bias is not None else None)
 
 
 # ================================================================================================ 1. the 1x1 GEMM

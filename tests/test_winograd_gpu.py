@@ -1,10 +1,13 @@
 """Winograd F(2x2, 3x3) kernels (r03) against fp64 torch, through the public C-ABI entry points.
 
 Two kernel families take the fp32 3x3 stride-1 convs on planes divisible by 16: ``conv_mfma_fwd_p<..., WINO>`` (reductions of
-16 / 32 channels, resident transformed weights) and ``conv_wino_l`` (csrc/conv_wino.hip: reductions >= 64 channels, weights
-transformed on the fly, 1 or 2 output-channel slabs per wave).  tests/test_ops_gpu.py pins the fused forms of a shape to each
-other bit for bit; here every form is pinned to an fp64 reference of reference network/blocks.py:10-12,53-80 arithmetic, on
-shapes that reach both families, both slab counts (Ndim % 32 != 0 forces one), odd batch sizes and image borders."""
+16 / 32 channels, resident transformed weights; only from 1024 units of N (H / 8) (W / 16) (Ndim / 16) on, ``fwd_p_eligible``) and
+``conv_wino_l`` (csrc/conv_wino.hip: reductions >= 64 channels, weights transformed on the fly, 1 or 2 output-channel slabs per
+wave).  tests/test_ops_gpu.py pins the fused forms of a shape to each other bit for bit; here every form is pinned to an fp64
+reference of reference network/blocks.py:10-12,53-80 arithmetic, on odd batch sizes and image borders.  The shapes below reach
+``conv_wino_l`` with ONE slab per wave only (two need items * (Ndim / 32) >= the CU count) and never the resident kernel: the three
+small-reduction shapes stay below its 1024 units and run the per-tile direct kernel ``conv_mfma_fwd`` -- each shape asserts the
+form ``smsut_conv2d_mfma_form`` reports.  The resident kernel, two slabs and the item walks are in tests/test_conv3x3_edges_gpu.py."""
 import numpy as np
 import pytest
 import torch
@@ -12,8 +15,11 @@ import torch.nn.functional as F
 
 pytestmark = pytest.mark.gpu
 
-SHAPES = [(3, 32, 16, 16), (2, 48, 32, 16), (5, 32, 16, 32),                  # resident form
-          (3, 32, 64, 64), (2, 48, 64, 48), (3, 16, 128, 64), (2, 32, 256, 128), (5, 16, 96, 32), (2, 64, 64, 32)]   # conv_wino_l
+SHAPES = [(3, 32, 16, 16), (2, 48, 32, 16), (5, 32, 16, 32),                  # 24 / 36 / 80 units < 1024: the per-tile direct kernel
+          (3, 32, 64, 64), (2, 48, 64, 48), (3, 16, 128, 64), (2, 32, 256, 128), (5, 16, 96, 32), (2, 64, 64, 32)]   # conv_wino_l, ntn = 1
+# smsut_conv2d_mfma_form of (forward, data-gradient) per shape: 0 direct, 1 resident Winograd, 2 streamed Winograd (conv_wino_l)
+FORMS = {(3, 32, 16, 16): (0, 0), (2, 48, 32, 16): (0, 0), (5, 32, 16, 32): (0, 0), (3, 32, 64, 64): (2, 2), (2, 48, 64, 48): (2, 0),
+         (3, 16, 128, 64): (2, 2), (2, 32, 256, 128): (2, 2), (5, 16, 96, 32): (2, 0), (2, 64, 64, 32): (2, 0)}
 
 
 def _mk(n, h, ci, co, seed):
@@ -68,6 +74,7 @@ def test_forward_datagrad_accumulate_statistics(n, h, ci, co, prepared):
     import smsut_amd  # noqa: F401
     from smsut_amd import _hip as H
     st = H.stream_ptr()
+    assert (H.call("smsut_conv2d_mfma_form", n, h, h, ci, co, 0), H.call("smsut_conv2d_mfma_form", n, h, h, co, ci, 0)) == FORMS[(n, h, ci, co)]
     g, x, w = _mk(n, h, ci, co, 3)
     keep = _Prepared(H, w, ci, co) if prepared else None  # noqa: F841
     ref = _conv64(x, w)
