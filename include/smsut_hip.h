@@ -629,13 +629,22 @@ int smsut_ema_chunk(void);
  *   border = mask XOR erosion(mask) with the 6-neighbour cross (4-neighbour when planar = 1, which needs D = 1) and the array
  *   faces outside the mask; distances are exact Euclidean in voxels (fp64 sqrt of integer squared distances), reduced in a
  *   fixed order: the result is bitwise reproducible.  A distance sum is meaningless when the other mask is empty.
- *   D, H, W <= 4096. */
+ *   D, H, W <= 4096.
+ * smsut_surface_hd: out = double[n_cls][6], per label, every entry an integer (medpy's hd / hd95 ingredients):
+ *   {border voxels of P, border voxels of G, largest squared distance from a border voxel of P to G's border, the same from G
+ *    to P, lo2, hi2}: with the squared distances of both directions pooled into one multiset of n values, lo2 is the one at
+ *   sorted rank lo = floor((double)(n - 1) * quantile) (one fp64 product) and hi2 the one at rank min(lo + 1, n - 1).  The four
+ *   distance entries are -1 when either mask is empty.  Borders, planar, limits and exactness as smsut_surface_stats; selected
+ *   through integer histograms (bitwise reproducible); 0 < quantile <= 1.  Its own workspace query. */
 int64_t smsut_cc_ws(int D, int H, int W, int n_cls, int per_slice);
 int smsut_cc_filter(const uint8_t* in, uint8_t* out, void* workspace, int D, int H, int W, int n_cls, int per_slice,
                     void* stream);
 int64_t smsut_surface_ws(int D, int H, int W, int n_cls, int planar);
 int smsut_surface_stats(const uint8_t* pred, const uint8_t* gt, double* out, void* workspace, int D, int H, int W, int n_cls,
                         int planar, void* stream);
+int64_t smsut_surface_hd_ws(int D, int H, int W, int n_cls, int planar);
+int smsut_surface_hd(const uint8_t* pred, const uint8_t* gt, double* out, void* workspace, int D, int H, int W, int n_cls,
+                     int planar, double quantile, void* stream);
 
 #ifdef __cplusplus
 }

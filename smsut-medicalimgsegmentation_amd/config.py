@@ -51,6 +51,7 @@ def class_weights(pair, labels=None):
 expr_root = "smsut_out"        # the reference's placeholder is '***/bimod-out' (config.py:46)
 base_root = None               # processed PNG dataset root ('***/bimod' upstream, config.py:44); None -> synthetic slices
 split_yaml = "semi-1910.yaml"  # config.py:54
+test_hausdorff = False         # -p test also writes {modality}_hd_matrix.csv (Hausdorff and HD95; commented out upstream)
 data_aug = dict(               # config.py:60-71
     rotate=True, rotate_degrees=15,
     resizeCrop=True, resizeCrop_size=input_size,

@@ -3,8 +3,12 @@
 //                        per-slice 8-neighbour union-find, Playne & Hawick 2018), components of <= 10 % of their class dropped;
 //   smsut_surface_stats  per label: Dice counts and, both ways, the border-voxel count and the fp64 sum of the exact Euclidean
 //                        distances from one mask's border to the other's (separable squared EDT: brute-force minimum over each
-//                        line's finite entries staged in LDS for x and y, the z pass fused with the gather).
-// No float atomics: fp64 partials per block, reduced in a fixed order (bitwise reproducible).
+//                        line's finite entries staged in LDS for x and y, the z pass fused with the gather);
+//   smsut_surface_hd     per label: the border-voxel counts, the largest squared distance each way and two order statistics
+//                        of the pooled squared distances (Hausdorff and its percentile, medpy's hd / hd95), by an exact
+//                        two-level radix select over LDS histograms.
+// No float atomics: fp64 partials per block, reduced in a fixed order; the histograms take integer atomics only (bitwise
+// reproducible).
 #include <algorithm>
 
 #include "common.h"
@@ -350,6 +354,218 @@ bool surf_args_ok(int D, int H, int W, int n_cls, int planar) {
 
 int line_block(int len) { return (int)std::min<int64_t>(SURF_BLOCK, cdiv64(len, 64) * 64); }
 
+// ---------------------------------------------------------------------------------------------- Hausdorff / percentile
+// Every squared distance is an integer below 2^26, so the maximum and any order statistic of a label's pooled distances are
+// exact: a two-level radix select, 13 bits a level, over the dense d^2 buffers the gather leaves (-1 off the border).  Counts
+// are unsigned (a pool holds at most 2 * D*H*W < 2^32 entries) and only integer atomics touch them: the result does not
+// depend on the order of arrival.
+constexpr int HD_SHIFT = 13;
+constexpr int HD_BINS = 1 << HD_SHIFT;
+constexpr int HD_LIMIT = 1 << (2 * HD_SHIFT);            // finite squared distances lie below it (3 * 4095^2 < 2^26)
+constexpr int HD_CTRL = 16;                              // control words of one label, ahead of its three histograms
+constexpr int HD_LABEL_WORDS = HD_CTRL + 3 * HD_BINS;    // hist 0: d^2 >> 13; hist 1, 2: d^2 & 8191 inside the bucket of rank lo, hi
+constexpr int HD_HIST_ITEMS = 16;                        // buffer entries per thread of a histogram block
+constexpr int HD_HIST_GRID_CAP = 1024;
+// control words: border voxels per direction, largest d^2 per direction, then (bucket, rank inside it) of the two ranks
+enum { HD_N = 0, HD_MAX = 2, HD_SEL = 4 };
+
+static_assert(HD_BINS == 32 * SURF_BLOCK, "hd_select gives every thread of one block 32 bins");
+static_assert(3LL * (SURF_MAX_DIM - 1) * (SURF_MAX_DIM - 1) < HD_LIMIT, "two levels must cover every finite squared distance");
+
+__global__ void hd_zero(unsigned* w, int64_t n) {
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) w[i] = 0;
+}
+
+// edt_gather's z pass, keeping every value: d2[i] = squared distance at the border voxels of `lab` in fa, -1 elsewhere;
+// part[block] = {border voxels, max d^2} (no global atomics here: thousands of waves on one address serialise in L2)
+__global__ __launch_bounds__(SURF_BLOCK) void edt_gather_d2(const uint8_t* __restrict__ fa, int lab, const int* __restrict__ g,
+                                                            int* __restrict__ d2, unsigned* __restrict__ part, int D, int H,
+                                                            int W, int planar) {
+  __shared__ unsigned red[2 * (SURF_BLOCK / 64)];
+  const int64_t HW = (int64_t)H * W, N = HW * D;
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  unsigned nb = 0, mx = 0;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < N; i += stride) {
+    const int z = (int)(i / HW);
+    const int64_t p = i - z * HW;
+    const int y = (int)(p / W), x = (int)(p % W);
+    int v = -1;
+    if (is_border(fa, lab, z, y, x, D, H, W, planar)) {
+      int best = SURF_INF;
+      for (int zz = 0; zz < D; ++zz) {
+        const int d = z - zz;
+        best = min(best, g[zz * HW + p] + d * d);
+      }
+      v = best;
+      nb += 1;
+      mx = max(mx, (unsigned)best);     // (>= SURF_INF when the other mask is empty: meaningless then, hd_final writes -1)
+    }
+    d2[i] = v;
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    nb += __shfl_xor(nb, o, 64);
+    mx = max(mx, __shfl_xor(mx, o, 64));
+  }
+  if ((threadIdx.x & 63) == 0) {
+    red[2 * (threadIdx.x / 64)] = nb;
+    red[2 * (threadIdx.x / 64) + 1] = mx;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    for (int k = 1; k < SURF_BLOCK / 64; ++k) {
+      nb += red[2 * k];
+      mx = max(mx, red[2 * k + 1]);
+    }
+    part[2 * blockIdx.x] = nb;
+    part[2 * blockIdx.x + 1] = mx;
+  }
+}
+
+// One key into the block's LDS histogram.  Segmentations give small distances: nearly every entry of the first level has key 0
+// and a handful of keys take the second, so the 64 atomics of a wave would serialise on one address.  As in photo_hist_add
+// (photometric.hip), HD_VOTE_ROUNDS values are taken out by vote first: the lanes that hold the first pending lane's key add
+// their popcount once; only what is left goes through per-lane atomics.
+#ifndef HD_VOTE_ROUNDS
+#define HD_VOTE_ROUNDS 1
+#endif
+__device__ __forceinline__ void hd_hist_add(unsigned* h, int key, bool valid) {
+  const int lane = threadIdx.x & 63;
+  bool rem = valid;
+#pragma unroll
+  for (int r = 0; r < HD_VOTE_ROUNDS; ++r) {
+    if (rem) {
+      const int k = __builtin_amdgcn_readfirstlane(key);
+      if (key == k) {
+        const unsigned long long same = __ballot(1);          // the active lanes: exactly those that hold k
+        if (lane == __ffsll((long long)same) - 1) atomicAdd(&h[k], (unsigned)__popcll(same));
+        rem = false;
+      }
+    }
+  }
+  if (rem) atomicAdd(&h[key], 1u);
+}
+
+// LEVEL 0: histogram of d^2 >> 13 over both directions' buffers; LEVEL 1 / 2: of d^2 & 8191 over the entries of the bucket that
+// holds rank lo / hi (level 2 only when the two buckets differ).  A label with an empty mask has no finite d^2 (SURF_INF lies
+// beyond the bins and is passed over): its first level stays empty, hd_pick records the zero count and the other levels return.
+template <int LEVEL>
+__global__ __launch_bounds__(SURF_BLOCK) void hd_hist(const int* __restrict__ d2, int64_t n2, unsigned* ctrl) {
+  __shared__ unsigned h[HD_BINS];
+  if (LEVEL && (ctrl[HD_N] == 0 || ctrl[HD_N + 1] == 0)) return;
+  const int bucket = LEVEL ? (int)ctrl[HD_SEL + 2 * (LEVEL - 1)] : 0;
+  if (LEVEL == 2 && bucket == (int)ctrl[HD_SEL]) return;
+  for (int k = threadIdx.x; k < HD_BINS; k += blockDim.x) h[k] = 0;
+  __syncthreads();
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n2; i += (int64_t)gridDim.x * blockDim.x) {
+    const int v = d2[i];
+    const bool valid = v >= 0 && v < HD_LIMIT && (LEVEL == 0 || (v >> HD_SHIFT) == bucket);
+    hd_hist_add(h, LEVEL ? (v & (HD_BINS - 1)) : (v >> HD_SHIFT), valid);
+  }
+  __syncthreads();
+  unsigned* hist = ctrl + HD_CTRL + LEVEL * HD_BINS;
+  for (int k = threadIdx.x; k < HD_BINS; k += blockDim.x)
+    if (h[k]) atomicAdd(hist + k, h[k]);
+}
+
+// the bin that holds sorted rank r of a histogram (r < its total): the smallest b with hist[0] + .. + hist[b] > r, and r minus
+// the counts below b.  One block of SURF_BLOCK threads, 32 bins each; sel[0..1] are written by the one thread whose range holds r.
+__device__ void hd_select(const unsigned* __restrict__ hist, unsigned long long r, unsigned long long* part, unsigned* sel) {
+  const int b0 = threadIdx.x * 32;
+  unsigned long long s = 0;
+  for (int b = b0; b < b0 + 32; ++b) s += hist[b];
+  __syncthreads();
+  part[threadIdx.x] = s;
+  __syncthreads();
+  unsigned long long acc = 0;
+  for (int k = 0; k < (int)threadIdx.x; ++k) acc += part[k];
+  if (r >= acc && r < acc + s) {
+    for (int b = b0; b < b0 + 32; ++b) {
+      const unsigned c = hist[b];
+      if (r < acc + c) {
+        sel[0] = (unsigned)b;
+        sel[1] = (unsigned)(r - acc);
+        break;
+      }
+      acc += c;
+    }
+  }
+}
+
+// after level 0: the gather blocks' partials to the label's counts and directed maxima, then the ranks
+// lo = floor((n - 1) * quantile) (one fp64 product, rounded once) and hi = min(lo + 1, n - 1) of the pooled distances, each to
+// its first-level bucket and its rank inside that bucket
+__global__ __launch_bounds__(SURF_BLOCK) void hd_pick(unsigned* ctrl, const unsigned* __restrict__ gpart, int G, double quantile) {
+  __shared__ unsigned long long part[SURF_BLOCK];
+  __shared__ unsigned tot[4];
+  if (threadIdx.x < 4) tot[threadIdx.x] = 0;
+  __syncthreads();
+  for (int dir = 0; dir < 2; ++dir) {
+    unsigned nb = 0, mx = 0;
+    for (int k = threadIdx.x; k < G; k += blockDim.x) {
+      nb += gpart[2 * (dir * G + k)];
+      mx = max(mx, gpart[2 * (dir * G + k) + 1]);
+    }
+    atomicAdd(&tot[HD_N + dir], nb);
+    atomicMax(&tot[HD_MAX + dir], mx);
+  }
+  __syncthreads();
+  if (threadIdx.x < 4) ctrl[threadIdx.x] = tot[threadIdx.x];
+  if (tot[HD_N] == 0 || tot[HD_N + 1] == 0) return;
+  const unsigned long long n = (unsigned long long)tot[HD_N] + tot[HD_N + 1];
+  unsigned long long lo = (unsigned long long)floor(__dmul_rn((double)(n - 1), quantile));
+  lo = lo < n - 1 ? lo : n - 1;
+  const unsigned long long hi = lo + 1 < n - 1 ? lo + 1 : n - 1;
+  hd_select(ctrl + HD_CTRL, lo, part, ctrl + HD_SEL);
+  hd_select(ctrl + HD_CTRL, hi, part, ctrl + HD_SEL + 2);
+}
+
+// out[l][6] = {border(P), border(G), max d^2 P -> G, max d^2 G -> P, d^2 at rank lo, d^2 at rank hi}; block l finishes label
+// l + 1 from its second-level histograms
+__global__ __launch_bounds__(SURF_BLOCK) void hd_final(const unsigned* __restrict__ ws, double* __restrict__ out) {
+  __shared__ unsigned long long part[SURF_BLOCK];
+  __shared__ unsigned bin[4];
+  const unsigned* ctrl = ws + (int64_t)blockIdx.x * HD_LABEL_WORDS;
+  double* o = out + 6 * (int64_t)blockIdx.x;
+  const unsigned n_pg = ctrl[HD_N], n_gp = ctrl[HD_N + 1];
+  if (n_pg == 0 || n_gp == 0) {
+    if (threadIdx.x == 0) {
+      o[0] = (double)n_pg;
+      o[1] = (double)n_gp;
+      for (int k = 2; k < 6; ++k) o[k] = -1.0;
+    }
+    return;
+  }
+  const unsigned b_lo = ctrl[HD_SEL], b_hi = ctrl[HD_SEL + 2];
+  hd_select(ctrl + HD_CTRL + HD_BINS, ctrl[HD_SEL + 1], part, bin);
+  hd_select(ctrl + HD_CTRL + (b_hi == b_lo ? 1 : 2) * HD_BINS, ctrl[HD_SEL + 3], part, bin + 2);
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    o[0] = (double)n_pg;
+    o[1] = (double)n_gp;
+    o[2] = (double)ctrl[HD_MAX];
+    o[3] = (double)ctrl[HD_MAX + 1];
+    o[4] = (double)((b_lo << HD_SHIFT) | bin[0]);
+    o[5] = (double)((b_hi << HD_SHIFT) | bin[2]);
+  }
+}
+
+struct HdLayout {
+  int64_t part, d2, g, bytes;     // byte offsets; every label's control words and histograms come first
+  int G;
+};
+
+HdLayout hd_layout(int D, int H, int W, int n_cls) {
+  const int64_t N = (int64_t)D * H * W;
+  HdLayout l;
+  l.G = (int)std::min<int64_t>(cdiv64(N, SURF_BLOCK), SURF_GRID_CAP);
+  l.part = cdiv64((int64_t)n_cls * HD_LABEL_WORDS * 4, 256) * 256;
+  l.d2 = l.part + cdiv64((int64_t)2 * l.G * 2 * 4, 256) * 256;
+  l.g = l.d2 + cdiv64(2 * N * 4, 256) * 256;
+  l.bytes = l.g + N * 4;
+  return l;
+}
+
 }  // namespace
 
 extern "C" {
@@ -410,6 +626,45 @@ int smsut_surface_stats(const uint8_t* pred, const uint8_t* gt, double* out, voi
     }
   }
   surf_final<<<2 * n_cls, SURF_BLOCK, 0, s>>>(cnt, part, out, l.G);
+  SMSUT_LAUNCH_CHECK();
+  return SMSUT_OK;
+}
+
+int64_t smsut_surface_hd_ws(int D, int H, int W, int n_cls, int planar) {
+  if (!surf_args_ok(D, H, W, n_cls, planar)) return -1;
+  return hd_layout(D, H, W, n_cls).bytes;
+}
+
+int smsut_surface_hd(const uint8_t* pred, const uint8_t* gt, double* out, void* workspace, int D, int H, int W, int n_cls,
+                     int planar, double quantile, void* stream) {
+  SMSUT_REQUIRE(pred && gt && out && workspace);
+  SMSUT_REQUIRE(surf_args_ok(D, H, W, n_cls, planar));
+  SMSUT_REQUIRE(quantile > 0.0 && quantile <= 1.0);      // (false for NaN)
+  const HdLayout l = hd_layout(D, H, W, n_cls);
+  char* ws = (char*)workspace;
+  unsigned* words = (unsigned*)ws;
+  unsigned* part = (unsigned*)(ws + l.part);     // one label's gather partials at a time: hd_pick reads them before the next
+  int* d2 = (int*)(ws + l.d2);
+  int* g = (int*)(ws + l.g);
+  const int64_t N = (int64_t)D * H * W;
+  const int hist_grid = (int)std::min<int64_t>(cdiv64(2 * N, (int64_t)SURF_BLOCK * HD_HIST_ITEMS), HD_HIST_GRID_CAP);
+  hipStream_t s = (hipStream_t)stream;
+  hd_zero<<<ew_grid((int64_t)n_cls * HD_LABEL_WORDS, SURF_BLOCK), SURF_BLOCK, 0, s>>>(words, (int64_t)n_cls * HD_LABEL_WORDS);
+  for (int lab = 1; lab <= n_cls; ++lab) {
+    unsigned* ctrl = words + (int64_t)(lab - 1) * HD_LABEL_WORDS;
+    for (int dir = 0; dir < 2; ++dir) {
+      const uint8_t* fa = dir ? gt : pred;
+      const uint8_t* fb = dir ? pred : gt;
+      edt_rows<<<(unsigned)(D * H), line_block(W), 0, s>>>(fb, lab, g, D, H, W, planar);
+      edt_cols<<<(unsigned)(D * W), line_block(H), 0, s>>>(g, H, W);
+      edt_gather_d2<<<l.G, SURF_BLOCK, 0, s>>>(fa, lab, g, d2 + dir * N, part + (int64_t)dir * l.G * 2, D, H, W, planar);
+    }
+    hd_hist<0><<<hist_grid, SURF_BLOCK, 0, s>>>(d2, 2 * N, ctrl);
+    hd_pick<<<1, SURF_BLOCK, 0, s>>>(ctrl, part, l.G, quantile);
+    hd_hist<1><<<hist_grid, SURF_BLOCK, 0, s>>>(d2, 2 * N, ctrl);
+    hd_hist<2><<<hist_grid, SURF_BLOCK, 0, s>>>(d2, 2 * N, ctrl);
+  }
+  hd_final<<<n_cls, SURF_BLOCK, 0, s>>>(words, out);
   SMSUT_LAUNCH_CHECK();
   return SMSUT_OK;
 }

@@ -2,7 +2,8 @@
 ``maybe_mkdir``; plus the Dice matrix of ``get_mo_matrix`` (:180-203) with medpy's ``dc`` restated from its
 formula (medpy is a third-party dependency that is not installed here; SURVEY.md 8c: parity unpinned), and the test
 table of ``get_all_matrix`` (:206-283) with ``connected_components`` (:18-36) and medpy's ``assd`` restated on the GPU
-(csrc/metrics.hip; skimage and medpy are not installed here either, the same unpinned parity)."""
+(csrc/metrics.hip; skimage and medpy are not installed here either, the same unpinned parity); and medpy's ``hd`` / ``hd95`` /
+``asd`` with ``get_hd_matrix``, the Hausdorff table the reference imported ``hd`` for and then left out."""
 import os
 from collections import OrderedDict
 from copy import deepcopy
@@ -83,22 +84,112 @@ def connected_components(pred):
     return ops.cc_filter(t, cfg.n_modal, per_slice=False).cpu().numpy()
 
 
+def _masks(result, reference, what):
+    a = _device_u8(np.asarray(result).astype(bool), what)
+    b = _device_u8(np.asarray(reference).astype(bool), what)
+    if a.shape != b.shape or a.dim() not in (2, 3):
+        raise ValueError(f"{what}: expected two 2-D or 3-D masks of one shape, got {tuple(a.shape)} and {tuple(b.shape)}")
+    return a, b
+
+
+def _raise_if_empty(n_result, n_reference):
+    if n_result == 0:
+        raise RuntimeError("The first supplied array does not contain any binary object.")
+    if n_reference == 0:
+        raise RuntimeError("The second supplied array does not contain any binary object.")
+
+
 def assd(result, reference):
     """medpy.metric.binary.assd with its defaults (unit spacing, erosion connectivity 1) on the GPU: the mean of the two
     average surface distances, each the mean over one mask's border voxels (mask XOR its erosion by the 6-neighbour cross,
     array faces outside) of the exact Euclidean distance to the other mask's border.  2-D or 3-D masks (nonzero = in);
     ``RuntimeError`` when either is empty, as medpy raises."""
     from .. import ops
-    a = _device_u8(np.asarray(result).astype(bool), "assd")
-    b = _device_u8(np.asarray(reference).astype(bool), "assd")
-    if a.shape != b.shape or a.dim() not in (2, 3):
-        raise ValueError(f"assd: expected two 2-D or 3-D masks of one shape, got {tuple(a.shape)} and {tuple(b.shape)}")
+    a, b = _masks(result, reference, "assd")
     st = ops.surface_stats(a, b, 1)[0]
-    if st[1] == 0:
-        raise RuntimeError("The first supplied array does not contain any binary object.")
-    if st[2] == 0:
-        raise RuntimeError("The second supplied array does not contain any binary object.")
+    _raise_if_empty(st[1], st[2])
     return 0.5 * (st[4] / st[3] + st[6] / st[5])
+
+
+def _hd_of(row):
+    """Hausdorff distance from one row of ``ops.surface_hd``: the square root of the larger directed maximum."""
+    return float(np.sqrt(max(row[2], row[3])))
+
+
+def _percentile_of(row, quantile):
+    """numpy.percentile (linear interpolation) of the pooled distances from one row of ``ops.surface_hd`` taken at
+    ``quantile``: the two neighbouring order statistics are exact square roots, the weight is the rank's fraction."""
+    n = row[0] + row[1]
+    pos = (n - 1) * quantile
+    a, b = np.sqrt(row[4]), np.sqrt(row[5])
+    return float(a + (b - a) * (pos - np.floor(pos)))
+
+
+def hd(result, reference):
+    """medpy.metric.binary.hd with its defaults (unit spacing, erosion connectivity 1) on the GPU: the largest distance from
+    a border voxel of either mask to the other mask's border -- the square root of an exact integer maximum.  2-D or 3-D
+    masks; ``RuntimeError`` when either is empty, as medpy raises."""
+    from .. import ops
+    a, b = _masks(result, reference, "hd")
+    row = ops.surface_hd(a, b, 1)[0]
+    _raise_if_empty(row[0], row[1])
+    return _hd_of(row)
+
+
+def hd95(result, reference):
+    """medpy.metric.binary.hd95 with its defaults on the GPU: ``numpy.percentile(numpy.hstack((d_pg, d_gp)), 95)`` of the two
+    directed sets of surface distances.  The device selects the two order statistics around rank (n - 1) * 0.95 exactly;
+    the host interpolates between their square roots.  ``RuntimeError`` when either mask is empty."""
+    from .. import ops
+    a, b = _masks(result, reference, "hd95")
+    row = ops.surface_hd(a, b, 1, q=95.0)[0]
+    _raise_if_empty(row[0], row[1])
+    return _percentile_of(row, 0.95)
+
+
+def asd(result, reference):
+    """medpy.metric.binary.asd with its defaults on the GPU: the mean over ``result``'s border voxels of the distance to
+    ``reference``'s border (directed; ``assd`` averages both directions).  ``RuntimeError`` when either mask is empty."""
+    from .. import ops
+    a, b = _masks(result, reference, "asd")
+    st = ops.surface_stats(a, b, 1)[0]
+    _raise_if_empty(st[1], st[2])
+    return st[4] / st[3]
+
+
+def get_hd_matrix(prd_npys, gt_npys):
+    """(Hausdorff, HD95) modality x organ matrices, each (n_modal + 1) x (n_label + 1) with the mean row and column: what the
+    reference's commented-out ``hd(predx, gx)`` (utils.py:245) and ``{modality}_hd_matrix.csv`` would have held, plus the
+    95th percentile.  Input checks, the two-stage cleanup and the per-modality averaging are ``get_all_matrix``'s; an organ
+    the cleaned prediction lacks takes, per metric, the running maximum of this volume's earlier organs (0 for the first);
+    an empty ground truth under a non-empty prediction raises RuntimeError."""
+    from .. import ops
+    hd_matrix = np.zeros((cfg.n_modal, cfg.n_label))
+    hd95_matrix = np.zeros((cfg.n_modal, cfg.n_label))
+    n = np.zeros((cfg.n_modal, 1))
+    for k in gt_npys.keys():
+        m = cfg.Modality[k.split("_")[0]].value
+        p = _device_u8(prd_npys[k], f"prediction {k}")
+        g = _device_u8(gt_npys[k], f"ground truth {k}")
+        if p.dim() != 3 or p.shape != g.shape:
+            raise ValueError(f"{k}: expected two [D, H, W] volumes of one shape, got {tuple(p.shape)} and {tuple(g.shape)}")
+        p1 = ops.cc_filter(p, cfg.n_modal, per_slice=False)
+        p1 = ops.cc_filter(p1, cfg.n_modal, per_slice=True)
+        rows = ops.surface_hd(p1, g, cfg.n_label, q=95.0)
+        maxhd, maxhd95 = 0, 0
+        for i in range(cfg.n_label):
+            if rows[i][0] == 0:
+                h, h95 = maxhd, maxhd95
+            elif rows[i][1] == 0:
+                raise RuntimeError("The second supplied array does not contain any binary object.")
+            else:
+                h, h95 = _hd_of(rows[i]), _percentile_of(rows[i], 0.95)
+            maxhd = maxhd if maxhd > h else h
+            maxhd95 = maxhd95 if maxhd95 > h95 else h95
+            hd_matrix[m][i] += h
+            hd95_matrix[m][i] += h95
+        n[m] += 1
+    return _full_matrix(hd_matrix, n), _full_matrix(hd95_matrix, n)
 
 
 def get_all_matrix(prd_npys, gt_npys):
@@ -107,7 +198,8 @@ def get_all_matrix(prd_npys, gt_npys):
     per organ j the Dice of the cleaned prediction and, if the prediction holds j, its ASSD to the ground truth -- else the
     running maximum of the ASSDs of this volume's earlier organs (0 for the first).  An empty ground truth under a
     non-empty prediction raises RuntimeError, as in the reference.  The second matrix is the reference's placeholder
-    (``t = s``, its hd call commented out): a copy of the Dice values.  Each volume is uploaded once; cleanup and surface
+    (``t = s``, its hd call commented out): a copy of the Dice values; ``get_hd_matrix`` computes the real Hausdorff and HD95
+    matrices.  Each volume is uploaded once; cleanup and surface
     statistics run on the device."""
     from .. import ops
     matrix = np.zeros((cfg.n_modal, cfg.n_label))

@@ -2421,3 +2421,20 @@ def surface_stats(pred_u8, gt_u8, n_cls):
     out = torch.empty(int(n_cls), 7, dtype=torch.float64, device=pred.device)
     H.call("smsut_surface_stats", pred, gt, out, ws, d, h, w, int(n_cls), planar, _s())
     return out.cpu().numpy()
+
+
+def surface_hd(pred_u8, gt_u8, n_cls, q=95.0):
+    """Per label 1..n_cls: float64 host array [n_cls, 6] of integers = {border(P), border(G), max d^2(border P -> border G),
+    max d^2(border G -> border P), lo2, hi2}: the squared distances of both directions pooled (n values), lo2 the one at
+    sorted rank lo = floor((n - 1) * q / 100) and hi2 the one at rank min(lo + 1, n - 1) -- medpy's hd / hd95 ingredients
+    (unit spacing, erosion connectivity 1), selected exactly on the device.  The four distance entries are -1 when either
+    mask is empty."""
+    pred, gt = pred_u8.contiguous(), gt_u8.contiguous()
+    if pred.shape != gt.shape:
+        raise ValueError(f"shape mismatch {tuple(pred.shape)} vs {tuple(gt.shape)}")
+    d, h, w, planar = _dhw(pred)
+    _dhw(gt)
+    ws = _byte_ws(H.call("smsut_surface_hd_ws", d, h, w, int(n_cls), planar), pred)
+    out = torch.empty(int(n_cls), 6, dtype=torch.float64, device=pred.device)
+    H.call("smsut_surface_hd", pred, gt, out, ws, d, h, w, int(n_cls), planar, float(q) / 100.0, _s())
+    return out.cpu().numpy()

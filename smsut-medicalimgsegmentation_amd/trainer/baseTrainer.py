@@ -22,7 +22,7 @@ from .. import config as cfg
 from .. import ops, parallel
 from ..misc.loss import DiceAndCrossEntropyLoss
 from ..misc.synthetic import SyntheticSliceLoader
-from ..misc.utils import Meter, get_all_matrix, get_mo_matrix, matrix_text, maybe_mkdir
+from ..misc.utils import Meter, get_all_matrix, get_hd_matrix, get_mo_matrix, matrix_text, maybe_mkdir
 
 
 def seed_all(seed=None):
@@ -410,7 +410,9 @@ class BaseTrainer(abc.ABC):
     def test(self, loader_type, expr_root):
         """baseTrainer.py:254-318: the raw Dice matrix (``dice_matrix.csv``, returned) and the reference's test table
         ``{modality}_trois_matrix.csv`` -- the Dice rows, an empty line, then the ASSD rows of ``get_all_matrix`` (connected-
-        component cleanup + average symmetric surface distance, on the GPU), '%.4f' values separated by ','; also logged."""
+        component cleanup + average symmetric surface distance, on the GPU), '%.4f' values separated by ','; also logged.
+        With ``cfg.test_hausdorff`` also ``{modality}_hd_matrix.csv`` (the file the reference left commented out, :293-303):
+        the Hausdorff rows, an empty line, then the HD95 rows of ``get_hd_matrix``, in the same layout and logged too."""
         _, _, loader = self.get_loaders(loader_type)
         gt = self._collect_labels(loader)
         n, prd = self.validate_epoch(loader, gt)
@@ -422,6 +424,12 @@ class BaseTrainer(abc.ABC):
         with open(pjoin(expr_root, f"{self.modality}_trois_matrix.csv"), "w") as f:
             f.write(log)
         self.info(log)
+        if cfg.test_hausdorff:
+            hd_matrix, hd95_matrix = get_hd_matrix(prd, gt)
+            log = matrix_text(hd_matrix) + "\n" + matrix_text(hd95_matrix)
+            with open(pjoin(expr_root, f"{self.modality}_hd_matrix.csv"), "w") as f:
+                f.write(log)
+            self.info(log)
         return mo
 
     def close(self):
