@@ -615,8 +615,8 @@ int smsut_ema_chunk(void);
 /* ---------------------------------------------------------------------------------------------- test-phase metrics
  * The `-p test` table of trainer/baseTrainer.py:254-318: get_all_matrix (misc/utils.py:206-283) cleans every predicted volume
  * with connected_components (misc/utils.py:18-36, skimage measure.label connectivity=2) in 3-D and then slice by slice, and
- * scores each organ with medpy's dc and assd (unit spacing, erosion connectivity 1).  Volumes are dense uint8 [D][H][W]; a 2-D
- * image is D = 1.  Workspaces are BYTES, from the matching *_ws query (-1 there: invalid arguments).
+ * scores each organ with medpy's dc and assd (erosion connectivity 1; in voxels, or with the _sp forms under a voxel
+ * spacing).  Volumes are dense uint8 [D][H][W]; a 2-D image is D = 1.  Workspaces are BYTES, from the matching *_ws query (-1 there: invalid arguments).
  *
  * smsut_cc_filter: out[v] = c where v lies in a component of class c in 1..n_cls (label value c; different classes never merge)
  *   whose size S satisfies (double)S > 0.1 * (double)F, F = the class's voxel count (per_slice = 1: in that slice), else 0 --
@@ -635,7 +635,17 @@ int smsut_ema_chunk(void);
  *    to P, lo2, hi2}: with the squared distances of both directions pooled into one multiset of n values, lo2 is the one at
  *   sorted rank lo = floor((double)(n - 1) * quantile) (one fp64 product) and hi2 the one at rank min(lo + 1, n - 1).  The four
  *   distance entries are -1 when either mask is empty.  Borders, planar, limits and exactness as smsut_surface_stats; selected
- *   through integer histograms (bitwise reproducible); 0 < quantile <= 1.  Its own workspace query. */
+ *   through integer histograms (bitwise reproducible); 0 < quantile <= 1.  Its own workspace query.
+ * smsut_surface_stats_sp, smsut_surface_hd_sp (workspaces from smsut_surface_sp_ws, smsut_surface_hd_sp_ws): the two above with
+ *   a voxel spacing (sz, sy, sx), ordered like the array axes, in any unit; sz is ignored when planar = 1.  Each spacing must lie
+ *   in [1e-100, 1e100] (so every squared distance, up to 3 * 4095^2 * s^2, is a normal finite double); otherwise the status is
+ *   SMSUT_EINVAL and nothing is launched.  Squared distances are fp64: min over the border voxels of
+ *   (sx*sx) * dx^2 + (sy*sy) * dy^2 + (sz*sz) * dz^2, the weights formed once, every product rounded before it is added (no
+ *   fma), the sums in x, y, z order.  At spacing (1, 1, 1) every output equals the unit entry point's bit for bit; scaling all
+ *   spacings by a power of two scales the distances by exactly it.  smsut_surface_stats_sp: the [n_cls][7] layout, distances in
+ *   the spacing's unit, the same fixed-order reduction (bitwise reproducible).  smsut_surface_hd_sp: the [n_cls][6] layout; the
+ *   four distance entries are fp64 SQUARED physical distances, each exactly one of the computed values (an exact five-level
+ *   radix select over the doubles' bit patterns, integer atomics only), -1 when either mask is empty. */
 int64_t smsut_cc_ws(int D, int H, int W, int n_cls, int per_slice);
 int smsut_cc_filter(const uint8_t* in, uint8_t* out, void* workspace, int D, int H, int W, int n_cls, int per_slice,
                     void* stream);
@@ -645,6 +655,12 @@ int smsut_surface_stats(const uint8_t* pred, const uint8_t* gt, double* out, voi
 int64_t smsut_surface_hd_ws(int D, int H, int W, int n_cls, int planar);
 int smsut_surface_hd(const uint8_t* pred, const uint8_t* gt, double* out, void* workspace, int D, int H, int W, int n_cls,
                      int planar, double quantile, void* stream);
+int64_t smsut_surface_sp_ws(int D, int H, int W, int n_cls, int planar);
+int smsut_surface_stats_sp(const uint8_t* pred, const uint8_t* gt, double* out, void* workspace, int D, int H, int W, int n_cls,
+                           int planar, double sz, double sy, double sx, void* stream);
+int64_t smsut_surface_hd_sp_ws(int D, int H, int W, int n_cls, int planar);
+int smsut_surface_hd_sp(const uint8_t* pred, const uint8_t* gt, double* out, void* workspace, int D, int H, int W, int n_cls,
+                        int planar, double quantile, double sz, double sy, double sx, void* stream);
 
 #ifdef __cplusplus
 }

@@ -52,6 +52,8 @@ expr_root = "smsut_out"        # the reference's placeholder is '***/bimod-out' 
 base_root = None               # processed PNG dataset root ('***/bimod' upstream, config.py:44); None -> synthetic slices
 split_yaml = "semi-1910.yaml"  # config.py:54
 test_hausdorff = False         # -p test also writes {modality}_hd_matrix.csv (Hausdorff and HD95; commented out upstream)
+test_spacing = None            # voxel spacing of the -p test surface distances: None (voxels), one (sz, sy, sx) for every volume,
+                               # or a mapping {volume key such as 'ct_001', or modality name such as 'ct': (sz, sy, sx)}
 data_aug = dict(               # config.py:60-71
     rotate=True, rotate_degrees=15,
     resizeCrop=True, resizeCrop_size=input_size,

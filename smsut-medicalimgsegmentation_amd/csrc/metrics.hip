@@ -6,7 +6,9 @@
 //                        line's finite entries staged in LDS for x and y, the z pass fused with the gather);
 //   smsut_surface_hd     per label: the border-voxel counts, the largest squared distance each way and two order statistics
 //                        of the pooled squared distances (Hausdorff and its percentile, medpy's hd / hd95), by an exact
-//                        two-level radix select over LDS histograms.
+//                        two-level radix select over LDS histograms;
+//   smsut_surface_stats_sp / smsut_surface_hd_sp  the same two with an anisotropic voxel spacing: fp64 weighted squared
+//                        distances through the same passes, and a five-level radix select over the doubles' bit patterns.
 // No float atomics: fp64 partials per block, reduced in a fixed order; the histograms take integer atomics only (bitwise
 // reproducible).
 #include <algorithm>
@@ -566,6 +568,320 @@ HdLayout hd_layout(int D, int H, int W, int n_cls) {
   return l;
 }
 
+// ---------------------------------------------------------------------------------------------- anisotropic voxel spacing
+// The same three passes with physical weights: squared distances are fp64, w = spacing^2 per axis (formed once on the host),
+//   rows    wx * dx^2                        (the minimum over the integer dx^2 first: the product is monotone in it)
+//   cols    min over y' of g(y') + wy * dy^2
+//   gather  min over z' of g(z') + wz * dz^2
+// dx^2, dy^2, dz^2 are integers below 2^24, converted exactly.  Every product is rounded on its own before it is added (the
+// library is built with -ffp-contract=fast; sp_rounded is photo_rounded's trick from photometric.hip in fp64), so each value
+// is one fixed expression of its inputs.  Two consequences the tests pin: with every weight 1 all values are the integers of
+// the kernels above (sums below 2^26 are exact), and scaling all weights by a power of two scales every value by exactly it.
+// "No feature" is +inf (a line without border voxels, the whole volume when the other mask is empty).
+constexpr double SP_MIN = 1e-100, SP_MAX = 1e100;      // spacing range: s^2 .. 3 * 4095^2 * s^2 stay normal finite doubles
+
+__device__ __forceinline__ double sp_rounded(double v) {
+  asm volatile("" : "+v"(v));
+  return v;
+}
+
+__device__ __forceinline__ double sp_inf() { return __longlong_as_double(0x7FF0000000000000LL); }
+
+__global__ __launch_bounds__(SURF_BLOCK) void edt_rows_sp(const uint8_t* __restrict__ fb, int lab, double* __restrict__ g, int D,
+                                                          int H, int W, int planar, double wx) {
+  __shared__ int pos[SURF_MAX_DIM];
+  __shared__ int npos;
+  const int row = blockIdx.x;
+  const int z = row / H, y = row % H;
+  if (threadIdx.x == 0) npos = 0;
+  __syncthreads();
+  for (int x = threadIdx.x; x < W; x += blockDim.x)
+    if (is_border(fb, lab, z, y, x, D, H, W, planar)) pos[atomicAdd(&npos, 1)] = x;
+  __syncthreads();
+  const int n = npos;
+  double* out = g + (int64_t)row * W;
+  for (int x = threadIdx.x; x < W; x += blockDim.x) {
+    int best = SURF_INF;
+    for (int k = 0; k < n; ++k) {
+      const int d = x - pos[k];
+      best = min(best, d * d);
+    }
+    out[x] = best < SURF_INF ? wx * (double)best : sp_inf();
+  }
+}
+
+__global__ __launch_bounds__(SURF_BLOCK) void edt_cols_sp(double* g, int H, int W, double wy) {
+  __shared__ double val[SURF_MAX_DIM];
+  __shared__ int pos[SURF_MAX_DIM];
+  __shared__ int npos;
+  const int z = blockIdx.x / W, x = blockIdx.x % W;
+  double* col = g + (int64_t)z * H * W + x;
+  if (threadIdx.x == 0) npos = 0;
+  __syncthreads();
+  for (int y = threadIdx.x; y < H; y += blockDim.x) {
+    const double v = col[(int64_t)y * W];
+    if (v < sp_inf()) {
+      const int k = atomicAdd(&npos, 1);
+      val[k] = v;
+      pos[k] = y;
+    }
+  }
+  __syncthreads();
+  const int n = npos;
+  for (int y = threadIdx.x; y < H; y += blockDim.x) {
+    double best = sp_inf();
+    for (int k = 0; k < n; ++k) {
+      const int d = y - pos[k];
+      best = fmin(best, val[k] + sp_rounded(wy * (double)(d * d)));
+    }
+    col[(int64_t)y * W] = best;
+  }
+}
+
+// the z pass at voxel (z, p) of the plane-major buffer g
+__device__ __forceinline__ double sp_zmin(const double* __restrict__ g, int z, int64_t p, int D, int64_t HW, double wz) {
+  double best = sp_inf();
+  for (int zz = 0; zz < D; ++zz) {
+    const int d = z - zz;
+    best = fmin(best, g[zz * HW + p] + sp_rounded(wz * (double)(d * d)));
+  }
+  return best;
+}
+
+// edt_gather with weights.  A border voxel that has no feature at all (the other mask is empty) adds sqrt(SURF_INF), what it
+// adds in edt_gather: the sum is as meaningless there as it is there, and the same number.
+__global__ __launch_bounds__(SURF_BLOCK) void edt_gather_sp(const uint8_t* __restrict__ fa, int lab, const double* __restrict__ g,
+                                                            double* __restrict__ part, int D, int H, int W, int planar,
+                                                            double wz) {
+  __shared__ double red[SURF_BLOCK / 64];
+  const int64_t HW = (int64_t)H * W, N = HW * D;
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  double nb = 0.0, sum = 0.0;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < N; i += stride) {
+    const int z = (int)(i / HW);
+    const int64_t p = i - z * HW;
+    const int y = (int)(p / W), x = (int)(p % W);
+    if (!is_border(fa, lab, z, y, x, D, H, W, planar)) continue;
+    const double best = sp_zmin(g, z, p, D, HW, wz);
+    nb += 1.0;
+    sum += sqrt(best < sp_inf() ? best : (double)SURF_INF);
+  }
+  nb = block_sum_d(nb, red);
+  sum = block_sum_d(sum, red);
+  if (threadIdx.x == 0) {
+    part[2 * blockIdx.x] = nb;
+    part[2 * blockIdx.x + 1] = sum;
+  }
+}
+
+SurfLayout surf_layout_sp(int D, int H, int W, int n_cls) {
+  SurfLayout l = surf_layout(D, H, W, n_cls);
+  l.bytes = l.g + (int64_t)D * H * W * 8;
+  return l;
+}
+
+bool spacing_ok(double s) { return s >= SP_MIN && s <= SP_MAX; }      // (false for NaN)
+
+bool surf_sp_args_ok(int planar, double sz, double sy, double sx) {
+  return (planar == 1 || spacing_ok(sz)) && spacing_ok(sy) && spacing_ok(sx);
+}
+
+// Hausdorff / percentile over fp64 squared distances.  A non-negative finite double orders as its bit pattern, so the key of
+// a value is its 63-bit integer image (off the border the buffer holds -1.0: a negative key).  An MSD radix select takes the key
+// of sorted rank lo in five levels of 13, 13, 13, 13 and 12 bits: level L histograms its digit over the entries whose higher
+// bits equal the prefix chosen so far (LDS histogram per workgroup, flushed with integer atomicAdd), one block scans the 8192
+// bins (hd_select above), extends the prefix and clears the bins for the next level.  After the last level the prefix IS the
+// value at rank lo.  Rank hi = min(lo + 1, n - 1) holds the same value unless lo is the last entry of that value; then it is
+// the smallest key above it, one integer atomicMin pass.  Only integer atomics: bitwise reproducible.  A label with an empty
+// mask is known from the counts before the first level; every later kernel returns at once for it.
+constexpr int SPH_LEVELS = 5;
+constexpr int SPH_CTRL = 8;      // 64-bit control words of one label
+enum { SPH_N = 0, SPH_MAX = 2, SPH_PREFIX = 4, SPH_RANK = 5, SPH_NEXT = 6, SPH_ABOVE = 7 };
+// SPH_N: border voxels per direction; SPH_MAX: bits of the largest d^2 per direction; SPH_PREFIX: the key bits chosen so far;
+// SPH_RANK: rank lo among the entries under the prefix; SPH_NEXT: before the last level 1 when hi = lo + 1, after it 1 when rank
+// hi holds another value than rank lo; SPH_ABOVE: the smallest key above the value at rank lo
+
+__host__ __device__ constexpr int sph_shift(int level) { return level < 4 ? 51 - 13 * level : 0; }      // 51, 38, 25, 12, 0
+__host__ __device__ constexpr int sph_bits(int level) { return level < 4 ? 13 : 12; }
+
+// edt_gather_d2 with weights: d2[i] = squared physical distance at the border voxels of `lab` in fa, -1.0 elsewhere;
+// part[block] = {border voxels, max d^2}
+__global__ __launch_bounds__(SURF_BLOCK) void edt_gather_d2_sp(const uint8_t* __restrict__ fa, int lab,
+                                                               const double* __restrict__ g, double* __restrict__ d2,
+                                                               double* __restrict__ part, int D, int H, int W, int planar,
+                                                               double wz) {
+  __shared__ double red[2 * (SURF_BLOCK / 64)];
+  const int64_t HW = (int64_t)H * W, N = HW * D;
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  double nb = 0.0, mx = 0.0;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < N; i += stride) {
+    const int z = (int)(i / HW);
+    const int64_t p = i - z * HW;
+    const int y = (int)(p / W), x = (int)(p % W);
+    double v = -1.0;
+    if (is_border(fa, lab, z, y, x, D, H, W, planar)) {
+      v = sp_zmin(g, z, p, D, HW, wz);
+      nb += 1.0;
+      mx = fmax(mx, v);      // (+inf when the other mask is empty: hd_final_sp writes -1 then)
+    }
+    d2[i] = v;
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    nb += __shfl_xor(nb, o, 64);      // counts below 2^31: every partial sum is exact
+    mx = fmax(mx, __shfl_xor(mx, o, 64));
+  }
+  if ((threadIdx.x & 63) == 0) {
+    red[2 * (threadIdx.x / 64)] = nb;
+    red[2 * (threadIdx.x / 64) + 1] = mx;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    for (int k = 1; k < SURF_BLOCK / 64; ++k) {
+      nb += red[2 * k];
+      mx = fmax(mx, red[2 * k + 1]);
+    }
+    part[2 * blockIdx.x] = nb;
+    part[2 * blockIdx.x + 1] = mx;
+  }
+}
+
+// the gather blocks' partials to the label's counts and directed maxima, rank lo as in hd_pick, and the select's start state
+__global__ __launch_bounds__(SURF_BLOCK) void hd_pick_sp(unsigned long long* ctrl, unsigned* hist, const double* __restrict__ gpart,
+                                                         int G, double quantile) {
+  __shared__ double s_nb[SURF_BLOCK], s_mx[SURF_BLOCK];
+  for (int k = threadIdx.x; k < HD_BINS; k += blockDim.x) hist[k] = 0;
+  double tot_n[2], tot_mx[2];
+  for (int dir = 0; dir < 2; ++dir) {
+    double nb = 0.0, mx = 0.0;
+    for (int k = threadIdx.x; k < G; k += blockDim.x) {
+      nb += gpart[2 * (dir * G + k)];
+      mx = fmax(mx, gpart[2 * (dir * G + k) + 1]);
+    }
+    __syncthreads();
+    s_nb[threadIdx.x] = nb;
+    s_mx[threadIdx.x] = mx;
+    __syncthreads();
+    nb = 0.0, mx = 0.0;
+    for (int k = 0; k < SURF_BLOCK; ++k) {
+      nb += s_nb[k];
+      mx = fmax(mx, s_mx[k]);
+    }
+    tot_n[dir] = nb;
+    tot_mx[dir] = mx;
+  }
+  if (threadIdx.x != 0) return;
+  const unsigned long long n_pg = (unsigned long long)tot_n[0], n_gp = (unsigned long long)tot_n[1];
+  ctrl[SPH_N] = n_pg;
+  ctrl[SPH_N + 1] = n_gp;
+  ctrl[SPH_MAX] = (unsigned long long)__double_as_longlong(tot_mx[0]);
+  ctrl[SPH_MAX + 1] = (unsigned long long)__double_as_longlong(tot_mx[1]);
+  unsigned long long lo = 0, n = n_pg + n_gp;
+  if (n_pg != 0 && n_gp != 0) {
+    lo = (unsigned long long)floor(__dmul_rn((double)(n - 1), quantile));
+    lo = lo < n - 1 ? lo : n - 1;
+  }
+  ctrl[SPH_PREFIX] = 0;
+  ctrl[SPH_RANK] = lo;
+  ctrl[SPH_NEXT] = (n_pg != 0 && n_gp != 0 && lo + 1 <= n - 1) ? 1 : 0;
+  ctrl[SPH_ABOVE] = ~0ull;
+}
+
+template <int LEVEL>
+__global__ __launch_bounds__(SURF_BLOCK) void hd_hist_sp(const long long* __restrict__ keys, int64_t n2,
+                                                         const unsigned long long* __restrict__ ctrl, unsigned* hist) {
+  __shared__ unsigned h[HD_BINS];
+  if (ctrl[SPH_N] == 0 || ctrl[SPH_N + 1] == 0) return;
+  constexpr int shift = sph_shift(LEVEL), bits = sph_bits(LEVEL);
+  constexpr int above = LEVEL ? shift + bits : 63;      // level 0: nothing above but the sign, and the prefix is 0
+  const long long prefix = (long long)ctrl[SPH_PREFIX];
+  for (int k = threadIdx.x; k < HD_BINS; k += blockDim.x) h[k] = 0;
+  __syncthreads();
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n2; i += (int64_t)gridDim.x * blockDim.x) {
+    const long long v = keys[i];
+    const bool valid = v >= 0 && (v >> above) == prefix;
+    hd_hist_add(h, (int)((v >> shift) & ((1 << bits) - 1)), valid);
+  }
+  __syncthreads();
+  for (int k = threadIdx.x; k < HD_BINS; k += blockDim.x)
+    if (h[k]) atomicAdd(hist + k, h[k]);
+}
+
+// one block: the bin of rank SPH_RANK in this level's histogram joins the prefix; the bins are cleared for the next level
+template <int LEVEL>
+__global__ __launch_bounds__(SURF_BLOCK) void hd_step_sp(unsigned long long* ctrl, unsigned* hist) {
+  __shared__ unsigned long long part[SURF_BLOCK];
+  __shared__ unsigned sel[2];
+  if (ctrl[SPH_N] == 0 || ctrl[SPH_N + 1] == 0) return;
+  hd_select(hist, ctrl[SPH_RANK], part, sel);
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    ctrl[SPH_PREFIX] = (ctrl[SPH_PREFIX] << sph_bits(LEVEL)) | sel[0];
+    ctrl[SPH_RANK] = sel[1];
+    if (LEVEL == SPH_LEVELS - 1) ctrl[SPH_NEXT] = (ctrl[SPH_NEXT] && sel[1] + 1 == hist[sel[0]]) ? 1 : 0;
+  }
+  __syncthreads();
+  for (int k = threadIdx.x; k < HD_BINS; k += blockDim.x) hist[k] = 0;
+}
+
+// the smallest key above the value at rank lo, only when rank hi needs it
+__global__ __launch_bounds__(SURF_BLOCK) void hd_above_sp(const long long* __restrict__ keys, int64_t n2, unsigned long long* ctrl) {
+  __shared__ unsigned long long m;
+  if (ctrl[SPH_N] == 0 || ctrl[SPH_N + 1] == 0 || ctrl[SPH_NEXT] == 0) return;
+  const long long v_lo = (long long)ctrl[SPH_PREFIX];
+  if (threadIdx.x == 0) m = ~0ull;
+  __syncthreads();
+  unsigned long long best = ~0ull;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n2; i += (int64_t)gridDim.x * blockDim.x) {
+    const long long v = keys[i];
+    if (v > v_lo) best = min(best, (unsigned long long)v);
+  }
+  if (best != ~0ull) atomicMin(&m, best);
+  __syncthreads();
+  if (threadIdx.x == 0 && m != ~0ull) atomicMin(ctrl + SPH_ABOVE, m);
+}
+
+// out[l][6] as hd_final, the four distance entries fp64 squared physical distances
+__global__ void hd_final_sp(const unsigned long long* __restrict__ ws, double* __restrict__ out, int n_cls) {
+  const int l = blockIdx.x * blockDim.x + threadIdx.x;
+  if (l >= n_cls) return;
+  const unsigned long long* ctrl = ws + (int64_t)l * SPH_CTRL;
+  double* o = out + 6 * (int64_t)l;
+  o[0] = (double)ctrl[SPH_N];
+  o[1] = (double)ctrl[SPH_N + 1];
+  if (ctrl[SPH_N] == 0 || ctrl[SPH_N + 1] == 0) {
+    for (int k = 2; k < 6; ++k) o[k] = -1.0;
+    return;
+  }
+  o[2] = __longlong_as_double((long long)ctrl[SPH_MAX]);
+  o[3] = __longlong_as_double((long long)ctrl[SPH_MAX + 1]);
+  o[4] = __longlong_as_double((long long)ctrl[SPH_PREFIX]);
+  o[5] = __longlong_as_double((long long)ctrl[ctrl[SPH_NEXT] ? SPH_ABOVE : SPH_PREFIX]);
+}
+
+struct HdSpLayout {
+  int64_t hist, part, d2, g, bytes;     // byte offsets; every label's control words come first, then the one histogram
+  int G;
+};
+
+HdSpLayout hd_layout_sp(int D, int H, int W, int n_cls) {
+  const int64_t N = (int64_t)D * H * W;
+  HdSpLayout l;
+  l.G = (int)std::min<int64_t>(cdiv64(N, SURF_BLOCK), SURF_GRID_CAP);
+  l.hist = cdiv64((int64_t)n_cls * SPH_CTRL * 8, 256) * 256;
+  l.part = l.hist + (int64_t)HD_BINS * 4;
+  l.d2 = l.part + cdiv64((int64_t)2 * l.G * 2 * 8, 256) * 256;
+  l.g = l.d2 + cdiv64(2 * N * 8, 256) * 256;
+  l.bytes = l.g + N * 8;
+  return l;
+}
+
+template <int LEVEL>
+void hd_level_sp(const long long* keys, int64_t n2, unsigned long long* ctrl, unsigned* hist, int hist_grid, hipStream_t s) {
+  hd_hist_sp<LEVEL><<<hist_grid, SURF_BLOCK, 0, s>>>(keys, n2, ctrl, hist);
+  hd_step_sp<LEVEL><<<1, SURF_BLOCK, 0, s>>>(ctrl, hist);
+}
+
 }  // namespace
 
 extern "C" {
@@ -665,6 +981,86 @@ int smsut_surface_hd(const uint8_t* pred, const uint8_t* gt, double* out, void* 
     hd_hist<2><<<hist_grid, SURF_BLOCK, 0, s>>>(d2, 2 * N, ctrl);
   }
   hd_final<<<n_cls, SURF_BLOCK, 0, s>>>(words, out);
+  SMSUT_LAUNCH_CHECK();
+  return SMSUT_OK;
+}
+
+int64_t smsut_surface_sp_ws(int D, int H, int W, int n_cls, int planar) {
+  if (!surf_args_ok(D, H, W, n_cls, planar)) return -1;
+  return surf_layout_sp(D, H, W, n_cls).bytes;
+}
+
+int smsut_surface_stats_sp(const uint8_t* pred, const uint8_t* gt, double* out, void* workspace, int D, int H, int W, int n_cls,
+                           int planar, double sz, double sy, double sx, void* stream) {
+  SMSUT_REQUIRE(pred && gt && out && workspace);
+  SMSUT_REQUIRE(surf_args_ok(D, H, W, n_cls, planar));
+  SMSUT_REQUIRE(surf_sp_args_ok(planar, sz, sy, sx));
+  const SurfLayout l = surf_layout_sp(D, H, W, n_cls);
+  char* ws = (char*)workspace;
+  unsigned long long* cnt = (unsigned long long*)ws;
+  double* part = (double*)(ws + l.part);
+  double* g = (double*)(ws + l.g);
+  const int64_t N = (int64_t)D * H * W;
+  const double wz = planar ? 1.0 : sz * sz, wy = sy * sy, wx = sx * sx;
+  hipStream_t s = (hipStream_t)stream;
+  surf_zero<<<1, SURF_BLOCK, 0, s>>>(cnt, 3 * n_cls);
+  surf_counts<<<ew_grid(N, SURF_BLOCK), SURF_BLOCK, 0, s>>>(pred, gt, cnt, N, n_cls);
+  for (int lab = 1; lab <= n_cls; ++lab) {
+    for (int dir = 0; dir < 2; ++dir) {
+      const uint8_t* fa = dir ? gt : pred;
+      const uint8_t* fb = dir ? pred : gt;
+      edt_rows_sp<<<(unsigned)(D * H), line_block(W), 0, s>>>(fb, lab, g, D, H, W, planar, wx);
+      edt_cols_sp<<<(unsigned)(D * W), line_block(H), 0, s>>>(g, H, W, wy);
+      double* p = part + (int64_t)(2 * (lab - 1) + dir) * l.G * 2;
+      edt_gather_sp<<<l.G, SURF_BLOCK, 0, s>>>(fa, lab, g, p, D, H, W, planar, wz);
+    }
+  }
+  surf_final<<<2 * n_cls, SURF_BLOCK, 0, s>>>(cnt, part, out, l.G);
+  SMSUT_LAUNCH_CHECK();
+  return SMSUT_OK;
+}
+
+int64_t smsut_surface_hd_sp_ws(int D, int H, int W, int n_cls, int planar) {
+  if (!surf_args_ok(D, H, W, n_cls, planar)) return -1;
+  return hd_layout_sp(D, H, W, n_cls).bytes;
+}
+
+int smsut_surface_hd_sp(const uint8_t* pred, const uint8_t* gt, double* out, void* workspace, int D, int H, int W, int n_cls,
+                        int planar, double quantile, double sz, double sy, double sx, void* stream) {
+  SMSUT_REQUIRE(pred && gt && out && workspace);
+  SMSUT_REQUIRE(surf_args_ok(D, H, W, n_cls, planar));
+  SMSUT_REQUIRE(quantile > 0.0 && quantile <= 1.0);      // (false for NaN)
+  SMSUT_REQUIRE(surf_sp_args_ok(planar, sz, sy, sx));
+  const HdSpLayout l = hd_layout_sp(D, H, W, n_cls);
+  char* ws = (char*)workspace;
+  unsigned long long* words = (unsigned long long*)ws;
+  unsigned* hist = (unsigned*)(ws + l.hist);     // one histogram and one set of gather partials: the labels run one after another
+  double* part = (double*)(ws + l.part);
+  double* d2 = (double*)(ws + l.d2);
+  double* g = (double*)(ws + l.g);
+  const long long* keys = (const long long*)d2;
+  const int64_t N = (int64_t)D * H * W;
+  const double wz = planar ? 1.0 : sz * sz, wy = sy * sy, wx = sx * sx;
+  const int hist_grid = (int)std::min<int64_t>(cdiv64(2 * N, (int64_t)SURF_BLOCK * HD_HIST_ITEMS), HD_HIST_GRID_CAP);
+  hipStream_t s = (hipStream_t)stream;
+  for (int lab = 1; lab <= n_cls; ++lab) {
+    unsigned long long* ctrl = words + (int64_t)(lab - 1) * SPH_CTRL;
+    for (int dir = 0; dir < 2; ++dir) {
+      const uint8_t* fa = dir ? gt : pred;
+      const uint8_t* fb = dir ? pred : gt;
+      edt_rows_sp<<<(unsigned)(D * H), line_block(W), 0, s>>>(fb, lab, g, D, H, W, planar, wx);
+      edt_cols_sp<<<(unsigned)(D * W), line_block(H), 0, s>>>(g, H, W, wy);
+      edt_gather_d2_sp<<<l.G, SURF_BLOCK, 0, s>>>(fa, lab, g, d2 + dir * N, part + (int64_t)dir * l.G * 2, D, H, W, planar, wz);
+    }
+    hd_pick_sp<<<1, SURF_BLOCK, 0, s>>>(ctrl, hist, part, l.G, quantile);
+    hd_level_sp<0>(keys, 2 * N, ctrl, hist, hist_grid, s);
+    hd_level_sp<1>(keys, 2 * N, ctrl, hist, hist_grid, s);
+    hd_level_sp<2>(keys, 2 * N, ctrl, hist, hist_grid, s);
+    hd_level_sp<3>(keys, 2 * N, ctrl, hist, hist_grid, s);
+    hd_level_sp<4>(keys, 2 * N, ctrl, hist, hist_grid, s);
+    hd_above_sp<<<hist_grid, SURF_BLOCK, 0, s>>>(keys, 2 * N, ctrl);
+  }
+  hd_final_sp<<<(unsigned)cdiv64(n_cls, 64), 64, 0, s>>>(words, out, n_cls);
   SMSUT_LAUNCH_CHECK();
   return SMSUT_OK;
 }

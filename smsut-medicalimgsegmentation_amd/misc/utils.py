@@ -99,14 +99,51 @@ def _raise_if_empty(n_result, n_reference):
         raise RuntimeError("The second supplied array does not contain any binary object.")
 
 
-def assd(result, reference):
-    """medpy.metric.binary.assd with its defaults (unit spacing, erosion connectivity 1) on the GPU: the mean of the two
-    average surface distances, each the mean over one mask's border voxels (mask XOR its erosion by the 6-neighbour cross,
-    array faces outside) of the exact Euclidean distance to the other mask's border.  2-D or 3-D masks (nonzero = in);
-    ``RuntimeError`` when either is empty, as medpy raises."""
+def _voxelspacing(voxelspacing, ndim):
+    """medpy's ``voxelspacing`` for an ``ndim``-axis array: None stays None (unit spacing, the integer kernels), a scalar is
+    broadcast to every axis, a sequence needs one entry per axis (``RuntimeError`` otherwise, as scipy's
+    ``_normalize_sequence`` raises through medpy); entries that are not finite and positive raise ``ValueError``.  Pure host
+    code: nothing touches the device."""
     from .. import ops
+    if voxelspacing is None:
+        return None
+    if np.ndim(voxelspacing) == 0:
+        voxelspacing = (voxelspacing,) * ndim
+    return ops.check_spacing(voxelspacing, ndim)
+
+
+def _spacings_for(spacings, keys):
+    """{volume key: (sz, sy, sx) or None} for ``get_all_matrix`` / ``get_hd_matrix``.  ``spacings``: None, one (sz, sy, sx)
+    for every volume, or a mapping in which a volume 'ct_001' is looked up by its own key first and then by its modality name
+    'ct'; a volume found under neither raises ``KeyError`` naming it.  Pure host code, run before any volume is uploaded."""
+    from collections.abc import Mapping
+    keys = list(keys)
+    if spacings is None:
+        return {k: None for k in keys}
+    if not isinstance(spacings, Mapping):
+        sp = _voxelspacing(spacings, 3)
+        return {k: sp for k in keys}
+    out = {}
+    for k in keys:
+        modality = k.split("_")[0]
+        if k in spacings:
+            out[k] = _voxelspacing(spacings[k], 3)
+        elif modality in spacings:
+            out[k] = _voxelspacing(spacings[modality], 3)
+        else:
+            raise KeyError(f"no voxel spacing for volume {k!r} (neither under {k!r} nor under its modality {modality!r})")
+    return out
+
+
+def assd(result, reference, voxelspacing=None):
+    """medpy.metric.binary.assd (erosion connectivity 1) on the GPU: the mean of the two average surface distances, each the
+    mean over one mask's border voxels (mask XOR its erosion by the 6-neighbour cross, array faces outside) of the exact
+    Euclidean distance to the other mask's border.  2-D or 3-D masks (nonzero = in); ``RuntimeError`` when either is empty,
+    as medpy raises.  ``voxelspacing``: None (distances in voxels), a scalar, or one value per array axis, medpy's meaning."""
+    from .. import ops
+    sp = _voxelspacing(voxelspacing, np.ndim(result))
     a, b = _masks(result, reference, "assd")
-    st = ops.surface_stats(a, b, 1)[0]
+    st = ops.surface_stats(a, b, 1, spacing=sp)[0]
     _raise_if_empty(st[1], st[2])
     return 0.5 * (st[4] / st[3] + st[6] / st[5])
 
@@ -125,45 +162,52 @@ def _percentile_of(row, quantile):
     return float(a + (b - a) * (pos - np.floor(pos)))
 
 
-def hd(result, reference):
-    """medpy.metric.binary.hd with its defaults (unit spacing, erosion connectivity 1) on the GPU: the largest distance from
-    a border voxel of either mask to the other mask's border -- the square root of an exact integer maximum.  2-D or 3-D
-    masks; ``RuntimeError`` when either is empty, as medpy raises."""
+def hd(result, reference, voxelspacing=None):
+    """medpy.metric.binary.hd (erosion connectivity 1) on the GPU: the largest distance from a border voxel of either mask
+    to the other mask's border -- the square root of an exact maximum of squared distances (integers without
+    ``voxelspacing``).  2-D or 3-D masks; ``RuntimeError`` when either is empty, as medpy raises.  ``voxelspacing`` as in
+    ``assd``."""
     from .. import ops
+    sp = _voxelspacing(voxelspacing, np.ndim(result))
     a, b = _masks(result, reference, "hd")
-    row = ops.surface_hd(a, b, 1)[0]
+    row = ops.surface_hd(a, b, 1, spacing=sp)[0]
     _raise_if_empty(row[0], row[1])
     return _hd_of(row)
 
 
-def hd95(result, reference):
-    """medpy.metric.binary.hd95 with its defaults on the GPU: ``numpy.percentile(numpy.hstack((d_pg, d_gp)), 95)`` of the two
-    directed sets of surface distances.  The device selects the two order statistics around rank (n - 1) * 0.95 exactly;
-    the host interpolates between their square roots.  ``RuntimeError`` when either mask is empty."""
+def hd95(result, reference, voxelspacing=None):
+    """medpy.metric.binary.hd95 on the GPU: ``numpy.percentile(numpy.hstack((d_pg, d_gp)), 95)`` of the two directed sets of
+    surface distances.  The device selects the two order statistics around rank (n - 1) * 0.95 exactly; the host
+    interpolates between their square roots.  ``RuntimeError`` when either mask is empty.  ``voxelspacing`` as in ``assd``."""
     from .. import ops
+    sp = _voxelspacing(voxelspacing, np.ndim(result))
     a, b = _masks(result, reference, "hd95")
-    row = ops.surface_hd(a, b, 1, q=95.0)[0]
+    row = ops.surface_hd(a, b, 1, q=95.0, spacing=sp)[0]
     _raise_if_empty(row[0], row[1])
     return _percentile_of(row, 0.95)
 
 
-def asd(result, reference):
-    """medpy.metric.binary.asd with its defaults on the GPU: the mean over ``result``'s border voxels of the distance to
-    ``reference``'s border (directed; ``assd`` averages both directions).  ``RuntimeError`` when either mask is empty."""
+def asd(result, reference, voxelspacing=None):
+    """medpy.metric.binary.asd on the GPU: the mean over ``result``'s border voxels of the distance to ``reference``'s border
+    (directed; ``assd`` averages both directions).  ``RuntimeError`` when either mask is empty.  ``voxelspacing`` as in
+    ``assd``."""
     from .. import ops
+    sp = _voxelspacing(voxelspacing, np.ndim(result))
     a, b = _masks(result, reference, "asd")
-    st = ops.surface_stats(a, b, 1)[0]
+    st = ops.surface_stats(a, b, 1, spacing=sp)[0]
     _raise_if_empty(st[1], st[2])
     return st[4] / st[3]
 
 
-def get_hd_matrix(prd_npys, gt_npys):
+def get_hd_matrix(prd_npys, gt_npys, spacings=None):
     """(Hausdorff, HD95) modality x organ matrices, each (n_modal + 1) x (n_label + 1) with the mean row and column: what the
     reference's commented-out ``hd(predx, gx)`` (utils.py:245) and ``{modality}_hd_matrix.csv`` would have held, plus the
     95th percentile.  Input checks, the two-stage cleanup and the per-modality averaging are ``get_all_matrix``'s; an organ
     the cleaned prediction lacks takes, per metric, the running maximum of this volume's earlier organs (0 for the first);
-    an empty ground truth under a non-empty prediction raises RuntimeError."""
+    an empty ground truth under a non-empty prediction raises RuntimeError.  ``spacings`` as in ``get_all_matrix``: both
+    matrices are then in the spacing's unit."""
     from .. import ops
+    spacing_of = _spacings_for(spacings, gt_npys.keys())
     hd_matrix = np.zeros((cfg.n_modal, cfg.n_label))
     hd95_matrix = np.zeros((cfg.n_modal, cfg.n_label))
     n = np.zeros((cfg.n_modal, 1))
@@ -175,7 +219,7 @@ def get_hd_matrix(prd_npys, gt_npys):
             raise ValueError(f"{k}: expected two [D, H, W] volumes of one shape, got {tuple(p.shape)} and {tuple(g.shape)}")
         p1 = ops.cc_filter(p, cfg.n_modal, per_slice=False)
         p1 = ops.cc_filter(p1, cfg.n_modal, per_slice=True)
-        rows = ops.surface_hd(p1, g, cfg.n_label, q=95.0)
+        rows = ops.surface_hd(p1, g, cfg.n_label, q=95.0, spacing=spacing_of[k])
         maxhd, maxhd95 = 0, 0
         for i in range(cfg.n_label):
             if rows[i][0] == 0:
@@ -192,7 +236,7 @@ def get_hd_matrix(prd_npys, gt_npys):
     return _full_matrix(hd_matrix, n), _full_matrix(hd95_matrix, n)
 
 
-def get_all_matrix(prd_npys, gt_npys):
+def get_all_matrix(prd_npys, gt_npys, spacings=None):
     """utils.py:206-283: (Dice, "Hausdorff", ASSD) modality x organ matrices, each (n_modal + 1) x (n_label + 1) with the
     mean row and column.  Per volume: connected_components in 3-D, then on every z slice alone (its own class totals);
     per organ j the Dice of the cleaned prediction and, if the prediction holds j, its ASSD to the ground truth -- else the
@@ -200,8 +244,12 @@ def get_all_matrix(prd_npys, gt_npys):
     non-empty prediction raises RuntimeError, as in the reference.  The second matrix is the reference's placeholder
     (``t = s``, its hd call commented out): a copy of the Dice values; ``get_hd_matrix`` computes the real Hausdorff and HD95
     matrices.  Each volume is uploaded once; cleanup and surface
-    statistics run on the device."""
+    statistics run on the device.  ``spacings``: None (ASSD in voxels), one ``(sz, sy, sx)`` for every volume, or a mapping
+    from a volume's key ('ct_001') or, failing that, its modality name ('ct') to its spacing (``KeyError`` naming the volume
+    that has neither); the ASSD matrix is then in the spacing's unit.  Dice, the cleanup and the running-maximum rule do not
+    depend on it."""
     from .. import ops
+    spacing_of = _spacings_for(spacings, gt_npys.keys())
     matrix = np.zeros((cfg.n_modal, cfg.n_label))
     hd_matrix = np.zeros((cfg.n_modal, cfg.n_label))
     assd_matrix = np.zeros((cfg.n_modal, cfg.n_label))
@@ -214,7 +262,7 @@ def get_all_matrix(prd_npys, gt_npys):
             raise ValueError(f"{k}: expected two [D, H, W] volumes of one shape, got {tuple(p.shape)} and {tuple(g.shape)}")
         p1 = ops.cc_filter(p, cfg.n_modal, per_slice=False)
         p1 = ops.cc_filter(p1, cfg.n_modal, per_slice=True)
-        st = ops.surface_stats(p1, g, cfg.n_label)
+        st = ops.surface_stats(p1, g, cfg.n_label, spacing=spacing_of[k])
         maxassd = 0
         for i in range(cfg.n_label):
             inter, n_p, n_g, b_p, s_p, b_g, s_g = st[i]

@@ -15,6 +15,7 @@ with other differentiable Functions), because WGAN-GP differentiates D's backwar
 from __future__ import annotations
 
 import contextlib
+import math
 import os as _os
 from typing import NamedTuple, Optional
 
@@ -2409,31 +2410,73 @@ def cc_filter(vol_u8, n_cls, per_slice):
     return out
 
 
-def surface_stats(pred_u8, gt_u8, n_cls):
+SPACING_MIN, SPACING_MAX = 1e-100, 1e100      # the range of the *_sp entry points (include/smsut_hip.h)
+
+
+def check_spacing(spacing, ndim):
+    """A voxel spacing for an ``ndim``-axis array as a tuple of floats, ordered like the axes.  Pure host code.  A sequence of
+    another length raises ``RuntimeError`` (what scipy's ``_normalize_sequence`` raises through medpy); an entry that is not
+    finite, not positive or outside [1e-100, 1e100] raises ``ValueError``."""
+    try:
+        sp = tuple(float(v) for v in spacing)
+    except TypeError:
+        raise RuntimeError("spacing must be a sequence with one entry per array axis") from None
+    if len(sp) != ndim:
+        raise RuntimeError("sequence argument must have length equal to input rank")
+    for v in sp:
+        if not (math.isfinite(v) and v > 0.0):
+            raise ValueError(f"voxel spacing must be finite and positive, got {sp}")
+        if not SPACING_MIN <= v <= SPACING_MAX:
+            raise ValueError(f"voxel spacing must lie in [{SPACING_MIN:g}, {SPACING_MAX:g}], got {sp}")
+    return sp
+
+
+def _zyx(spacing, ndim):
+    sp = check_spacing(spacing, ndim)
+    return (1.0, *sp) if ndim == 2 else sp
+
+
+def surface_stats(pred_u8, gt_u8, n_cls, spacing=None):
     """Per label 1..n_cls: float64 host array [n_cls, 7] = {|P&G|, |P|, |G|, border(P), sum dist(border P -> border G),
-    border(G), sum dist(border G -> border P)} (medpy's dc / assd ingredients at unit spacing, erosion connectivity 1)."""
+    border(G), sum dist(border G -> border P)} (medpy's dc / assd ingredients, erosion connectivity 1).  ``spacing``: None for
+    distances in voxels, else one positive finite float per array axis, ``(sz, sy, sx)`` or ``(sy, sx)`` (medpy's
+    ``voxelspacing``): the distances are then in the spacing's unit."""
     pred, gt = pred_u8.contiguous(), gt_u8.contiguous()
     if pred.shape != gt.shape:
         raise ValueError(f"shape mismatch {tuple(pred.shape)} vs {tuple(gt.shape)}")
     d, h, w, planar = _dhw(pred)
     _dhw(gt)
+    if spacing is not None:
+        sp = _zyx(spacing, pred.dim())
+        ws = _byte_ws(H.call("smsut_surface_sp_ws", d, h, w, int(n_cls), planar), pred)
+        out = torch.empty(int(n_cls), 7, dtype=torch.float64, device=pred.device)
+        H.call("smsut_surface_stats_sp", pred, gt, out, ws, d, h, w, int(n_cls), planar, *sp, _s())
+        return out.cpu().numpy()
     ws = _byte_ws(H.call("smsut_surface_ws", d, h, w, int(n_cls), planar), pred)
     out = torch.empty(int(n_cls), 7, dtype=torch.float64, device=pred.device)
     H.call("smsut_surface_stats", pred, gt, out, ws, d, h, w, int(n_cls), planar, _s())
     return out.cpu().numpy()
 
 
-def surface_hd(pred_u8, gt_u8, n_cls, q=95.0):
-    """Per label 1..n_cls: float64 host array [n_cls, 6] of integers = {border(P), border(G), max d^2(border P -> border G),
+def surface_hd(pred_u8, gt_u8, n_cls, q=95.0, spacing=None):
+    """Per label 1..n_cls: float64 host array [n_cls, 6] = {border(P), border(G), max d^2(border P -> border G),
     max d^2(border G -> border P), lo2, hi2}: the squared distances of both directions pooled (n values), lo2 the one at
     sorted rank lo = floor((n - 1) * q / 100) and hi2 the one at rank min(lo + 1, n - 1) -- medpy's hd / hd95 ingredients
-    (unit spacing, erosion connectivity 1), selected exactly on the device.  The four distance entries are -1 when either
-    mask is empty."""
+    (erosion connectivity 1), selected exactly on the device.  The four distance entries are -1 when either mask is empty.
+    ``spacing``: None for voxels (the four distance entries are then integers), else one positive finite float per array
+    axis, ``(sz, sy, sx)`` or ``(sy, sx)``: the four distance columns are then fp64 SQUARED physical distances, each exactly
+    one of the values the device computed."""
     pred, gt = pred_u8.contiguous(), gt_u8.contiguous()
     if pred.shape != gt.shape:
         raise ValueError(f"shape mismatch {tuple(pred.shape)} vs {tuple(gt.shape)}")
     d, h, w, planar = _dhw(pred)
     _dhw(gt)
+    if spacing is not None:
+        sp = _zyx(spacing, pred.dim())
+        ws = _byte_ws(H.call("smsut_surface_hd_sp_ws", d, h, w, int(n_cls), planar), pred)
+        out = torch.empty(int(n_cls), 6, dtype=torch.float64, device=pred.device)
+        H.call("smsut_surface_hd_sp", pred, gt, out, ws, d, h, w, int(n_cls), planar, float(q) / 100.0, *sp, _s())
+        return out.cpu().numpy()
     ws = _byte_ws(H.call("smsut_surface_hd_ws", d, h, w, int(n_cls), planar), pred)
     out = torch.empty(int(n_cls), 6, dtype=torch.float64, device=pred.device)
     H.call("smsut_surface_hd", pred, gt, out, ws, d, h, w, int(n_cls), planar, float(q) / 100.0, _s())

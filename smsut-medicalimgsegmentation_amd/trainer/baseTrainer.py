@@ -412,20 +412,25 @@ class BaseTrainer(abc.ABC):
         ``{modality}_trois_matrix.csv`` -- the Dice rows, an empty line, then the ASSD rows of ``get_all_matrix`` (connected-
         component cleanup + average symmetric surface distance, on the GPU), '%.4f' values separated by ','; also logged.
         With ``cfg.test_hausdorff`` also ``{modality}_hd_matrix.csv`` (the file the reference left commented out, :293-303):
-        the Hausdorff rows, an empty line, then the HD95 rows of ``get_hd_matrix``, in the same layout and logged too."""
+        the Hausdorff rows, an empty line, then the HD95 rows of ``get_hd_matrix``, in the same layout and logged too.
+        With ``cfg.test_spacing`` (one (sz, sy, sx), or a mapping by volume key or modality name) the ASSD, Hausdorff and HD95
+        rows are in that spacing's unit and the log says which spacing was used; None: voxels, the same bytes as ever."""
         _, _, loader = self.get_loaders(loader_type)
         gt = self._collect_labels(loader)
         n, prd = self.validate_epoch(loader, gt)
         mo = get_mo_matrix(prd, gt)
         maybe_mkdir(expr_root)
         np.savetxt(pjoin(expr_root, "dice_matrix.csv"), mo, delimiter=",", fmt="%.6f")
-        _, _, assd_matrix = get_all_matrix(prd, gt)
+        spacing = {} if cfg.test_spacing is None else {"spacings": cfg.test_spacing}
+        if spacing:
+            self.info(f"surface distances (ASSD, Hausdorff, HD95) at voxel spacing {cfg.test_spacing!r} (sz, sy, sx)")
+        _, _, assd_matrix = get_all_matrix(prd, gt, **spacing)
         log = matrix_text(mo) + "\n" + matrix_text(assd_matrix)
         with open(pjoin(expr_root, f"{self.modality}_trois_matrix.csv"), "w") as f:
             f.write(log)
         self.info(log)
         if cfg.test_hausdorff:
-            hd_matrix, hd95_matrix = get_hd_matrix(prd, gt)
+            hd_matrix, hd95_matrix = get_hd_matrix(prd, gt, **spacing)
             log = matrix_text(hd_matrix) + "\n" + matrix_text(hd95_matrix)
             with open(pjoin(expr_root, f"{self.modality}_hd_matrix.csv"), "w") as f:
                 f.write(log)
