@@ -612,6 +612,32 @@ int smsut_cora_pseudo(const float* z, int64_t* q, float* m, int64_t P, int L, vo
 int smsut_ema_multi(const void* ents, const int* blk_ent, const int* blk_chunk, int nblocks, float alpha, float beta, void* stream);
 int smsut_ema_chunk(void);
 
+/* ---------------------------------------------------------------------------------------------- dual-task consistency (DTC)
+ * network/dtc.py's two heads (tanh level-set regression t, segmentation logits z) need, per iteration, the normalised signed distance
+ * map of every class of every labelled slice, and a two-term loss.  csrc/dtc.hip.
+ *
+ * smsut_edt_sq: labels int64 [B][H][W] -> d2 int32 [B][C][H][W].  With P = (label == c): d2 = the exact squared Euclidean distance from
+ *   the pixel to the nearest pixel whose membership in P differs from its own (members: nearest non-member = scipy's
+ *   distance_transform_edt(P)^2; non-members: nearest member = distance_transform_edt(~P)^2).  Outside the image is nothing; d2 = 0
+ *   everywhere where P is empty or full.  1 <= H, W <= 512, 1 <= C <= 16, B * C <= 65535; otherwise SMSUT_EINVAL (smsut_sdf_ws: -1).
+ *   workspace: smsut_sdf_ws(B, C, H, W) floats; it keeps the two per-image maxima for smsut_sdf_final.  status: one device int that a
+ *   label outside [0, C) sets to 1 (such a pixel is a member of no class); it is never cleared or read here.
+ * smsut_sdf_final: sdf fp32 [B][H][W][C] (NHWC) = +sqrt(d2 / max of d2 over the non-members) on non-members,
+ *   -sqrt(d2 / max over the members) on members, exactly 0 on the inner boundary (members with d2 == 1), exactly +1 everywhere where P is
+ *   empty and -1 where P is full.  One fp64 division and square root, rounded to fp32 once.
+ * smsut_dtc_loss_fwd: t, z fp32 [N][HW][C], sdf [B][HW][C] pairing with the first B slices (1 <= B <= N), 1 <= C <= 16:
+ *   out[2] = [mean over B C HW of (t - sdf)^2, mean over N C HW of (sigmoid(-k t) - softmax(z)_c)^2]; workgroup partials in double,
+ *   summed in a fixed order (bitwise reproducible); finite for every t in [-1, 1] and any k.  workspace: smsut_dtc_ws(N, HW) floats.
+ * smsut_dtc_loss_bwd: gt = gout[0] d out[0]/dt + gout[1] d out[1]/dt and gz = gout[1] d out[1]/dz in one launch (no gradient to sdf). */
+int64_t smsut_sdf_ws(int B, int C, int H, int W);
+int smsut_edt_sq(const int64_t* labels, int* d2, float* workspace, int* status, int B, int C, int H, int W, void* stream);
+int smsut_sdf_final(const int64_t* labels, const int* d2, const float* workspace, float* sdf, int B, int C, int H, int W, void* stream);
+int64_t smsut_dtc_ws(int N, int64_t HW);
+int smsut_dtc_loss_fwd(const float* t, const float* z, const float* sdf, float* out /*2*/, float* workspace, int N, int B, int64_t HW,
+                       int C, float k, void* stream);
+int smsut_dtc_loss_bwd(const float* t, const float* z, const float* sdf, const float* gout /*2*/, float* gt, float* gz, int N, int B,
+                       int64_t HW, int C, float k, void* stream);
+
 /* ---------------------------------------------------------------------------------------------- test-phase metrics
  * The `-p test` table of trainer/baseTrainer.py:254-318: get_all_matrix (misc/utils.py:206-283) cleans every predicted volume
  * with connected_components (misc/utils.py:18-36, skimage measure.label connectivity=2) in 3-D and then slice by slice, and

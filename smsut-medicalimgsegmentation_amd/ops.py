@@ -2193,6 +2193,114 @@ def cora_pseudo(logits):
     return q, m
 
 
+# ------------------------------------------------------------------------------------------- dual-task consistency (csrc/dtc.hip)
+_SDF_STATUS = {}         # device -> one int32 that smsut_edt_sq sets when it meets a label outside [0, C); read by sdf_check() only
+#                          (allocated by the first call on a device: make that call eagerly, NOT inside a graph capture, or the word
+#                          would live in the capture's private pool)
+
+
+def _sdf_status(dev):
+    st = _SDF_STATUS.get(dev)
+    if st is None:
+        st = _SDF_STATUS[dev] = torch.zeros(1, dtype=torch.int32, device=dev)
+    return st
+
+
+def _sdf_labels(labels, n_classes, what):
+    if labels.dtype != torch.int64 or labels.dim() != 3:
+        raise TypeError(f"{what}: labels must be torch.int64 of shape [B, H, W], got {labels.dtype} {tuple(labels.shape)}")
+    b, h, w = labels.shape
+    n_classes = int(n_classes)
+    ws = H.call("smsut_sdf_ws", b, n_classes, h, w)
+    if ws < 0:
+        raise ValueError(f"{what}: needs 1 <= H, W <= 512 and 1 <= n_classes <= 16, got H = {h}, W = {w}, n_classes = {n_classes}")
+    return labels.contiguous(), n_classes, ws
+
+
+def _edt_launch(labels, n_classes, ws):
+    b, h, w = labels.shape
+    d2 = torch.empty(b, n_classes, h, w, dtype=torch.int32, device=labels.device)
+    work = _ws(ws, labels)
+    H.call("smsut_edt_sq", labels, d2, work, _sdf_status(labels.device), b, n_classes, h, w, _s())
+    return d2, work
+
+
+def sdf_check(device=None):
+    """Raise ``ValueError`` if an ``edt_sq`` / ``signed_distance_map`` call on ``device`` since the last check met a label outside
+    ``[0, n_classes)``.  The kernels only SET a device word (such a pixel counts as a member of no class); this reads it, so it
+    synchronises: call it where the host waits anyway (the trainer does after reading the iteration's scalars), never inside a capture."""
+    dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+    st = _SDF_STATUS.get(dev)
+    if st is not None and st.item() != 0:
+        st.zero_()
+        raise ValueError("signed_distance_map / edt_sq: a label lies outside [0, n_classes)")
+
+
+def edt_sq(labels, n_classes, validate=False):
+    """Exact squared Euclidean distance transform of every class of every label slice: int64 labels ``[B, H, W]`` -> int32
+    ``[B, n_classes, H, W]``.  With ``P = (labels == c)`` a member of P gets the squared distance to the nearest non-member
+    (``scipy.ndimage.distance_transform_edt(P) ** 2``) and a non-member the squared distance to the nearest member
+    (``distance_transform_edt(~P) ** 2``); outside the image is nothing, and the result is 0 everywhere where P is empty or full.
+    Two launches on the current stream, nothing read back; ``validate=True`` adds ``sdf_check()`` (one synchronisation).  Capturable into
+    a graph after one eager call on the device (the first call allocates the status word and sets a kernel attribute)."""
+    labels, n_classes, ws = _sdf_labels(labels, n_classes, "edt_sq")
+    d2, _ = _edt_launch(labels, n_classes, ws)
+    if validate:
+        sdf_check(labels.device)
+    return d2
+
+
+def signed_distance_map(labels, n_classes, validate=False):
+    """The DTC supervision target: fp32 ``[B, n_classes, H, W]`` in channels-last memory (the layout of the tanh head), per class
+    ``+sqrt(d2) / sqrt(max d2 over the non-members)`` on non-members and ``-sqrt(d2) / sqrt(max d2 over the members)`` on members with
+    ``d2 = edt_sq``; exactly 0 on the inner boundary (members with ``d2 == 1``), exactly +1 everywhere where the class is absent from the
+    slice and -1 where it fills it.  No autograd; three launches on the current stream, nothing read back (``validate`` as ``edt_sq``)."""
+    labels, n_classes, ws = _sdf_labels(labels, n_classes, "signed_distance_map")
+    b, h, w = labels.shape
+    d2, work = _edt_launch(labels, n_classes, ws)
+    sdf = torch.empty(b, h, w, n_classes, dtype=torch.float32, device=labels.device).permute(0, 3, 1, 2)
+    H.call("smsut_sdf_final", labels, d2, work, sdf, b, n_classes, h, w, _s())
+    if validate:
+        sdf_check(labels.device)
+    return sdf
+
+
+class DtcLossFn(Function):
+    """[mean((t[:B] - sdf) ** 2), mean((sigmoid(-k t) - softmax(z, 1)) ** 2)]; one backward launch writes d/dt and d/dz."""
+
+    @staticmethod
+    def forward(ctx, t, z, sdf, k):
+        t, z, sdf = nhwc(t), nhwc(z), nhwc(sdf)
+        if t.shape != z.shape:
+            raise ValueError(f"dtc_loss: the two heads differ in shape: {tuple(t.shape)} vs {tuple(z.shape)}")
+        n, c, h, w = t.shape
+        b = sdf.shape[0]
+        if tuple(sdf.shape[1:]) != (c, h, w) or not 1 <= b <= n or sdf.dtype != torch.float32:
+            raise ValueError(f"dtc_loss: sdf must be fp32 [B <= {n}, {c}, {h}, {w}], got {sdf.dtype} {tuple(sdf.shape)}")
+        out = torch.empty(2, dtype=torch.float32, device=t.device)
+        H.call("smsut_dtc_loss_fwd", t, z, sdf, out, _ws(H.call("smsut_dtc_ws", n, h * w), t), n, b, h * w, c, float(k), _s())
+        ctx.save_for_backward(t, z, sdf)
+        ctx.k = float(k)
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gout):
+        t, z, sdf = ctx.saved_tensors
+        n, c, h, w = t.shape
+        gt, gz = new_act(n, c, h, w, t), new_act(n, c, h, w, z)
+        H.call("smsut_dtc_loss_bwd", t, z, sdf, gout.contiguous(), gt, gz, n, sdf.shape[0], h * w, c, ctx.k, _s())
+        return gt, gz, None, None
+
+
+def dtc_loss(t, z, sdf, k=1500.0):
+    """The two DTC terms as the device tensor ``[L_sdf, L_cons]``: ``t`` the tanh head and ``z`` the logits, both ``[N, C, H, W]``;
+    ``sdf`` ``[B, C, H, W]`` (``signed_distance_map``; no gradient) pairs with the first ``B <= N`` slices.
+    ``L_sdf = mean((t[:B] - sdf) ** 2)``, ``L_cons = mean((sigmoid(-k * t) - softmax(z, 1)) ** 2)`` over all N slices.  Both are local
+    means (per rank under data parallelism, like ``softmax_mse``), bit-identical from run to run, finite for every t in [-1, 1]."""
+    return DtcLossFn.apply(cl(t), cl(z), cl(sdf).detach(), k)
+
+
 def _dense(t):
     """Every element of the storage span belongs to exactly one index (any dimension order)."""
     exp = 1

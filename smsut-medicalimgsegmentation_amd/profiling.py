@@ -215,6 +215,12 @@ _BYTES: Dict[str, Callable[[List[int]], float]] = {
     "smsut_act_bwd": lambda a: 4.0 * a[0] * 3,
     "smsut_tanh_fwd": lambda a: 4.0 * a[0] * 2,
     "smsut_tanh_bwd": lambda a: 4.0 * a[0] * 3,
+    # dual-task consistency (dtc.hip).  (b, c, h, w): labels int64 in, d2 int32 out (+ the membership words, written and read once)
+    "smsut_edt_sq": lambda a: a[0] * a[2] * a[3] * (8.0 + 4.0 * a[1] + 2.0 * a[1] / 8.0),
+    "smsut_sdf_final": lambda a: a[0] * a[2] * a[3] * (8.0 + 4.0 * a[1] + 4.0 * a[1]),                # labels, d2 -> sdf
+    # (n, b, hw, c): t, z over n slices, sdf over b
+    "smsut_dtc_loss_fwd": lambda a: 4.0 * a[2] * a[3] * (2 * a[0] + a[1]),
+    "smsut_dtc_loss_bwd": lambda a: 4.0 * a[2] * a[3] * (4 * a[0] + a[1]),                             # + gt, gz
 }
 
 

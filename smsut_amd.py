@@ -25,9 +25,9 @@ def _load():
 
 
 _DROPIN = ("config", "network", "network.blocks", "network.unet", "network.ugan", "network.networks",
-           "network.patchnce", "misc", "misc.loss", "misc.utils", "trainer", "trainer.baseTrainer",
+           "network.patchnce", "network.dtc", "misc", "misc.loss", "misc.utils", "trainer", "trainer.baseTrainer",
            "trainer.unetTrainer", "trainer.uganShp0Trainer", "trainer.uganConsisTrainer", "trainer.uganTrainer",
-           "trainer.meanTeacherTrainer", "trainer.crossPseTrainer", "trainer.coraNetTrainer")
+           "trainer.meanTeacherTrainer", "trainer.crossPseTrainer", "trainer.coraNetTrainer", "trainer.dtcTrainer")
 
 
 def install_dropin():
