@@ -852,15 +852,32 @@ restail_bwd_apply(const float* __restrict__ gout, const float* __restrict__ out,
       }
       ld_act<VEC, HS>(t.y2, (size_t)i * VEC, y);
       if (t.ms) ld_act<VEC, HS>(t.s, (size_t)i * VEC, sv);
+      // gz - a - xhat * b as two fmas (both products unrounded), written out.  Left to -ffp-contract the compiler chose per
+      // instantiation AND per branch of img_walk: the VEC = 4 forms fused both products everywhere except the AMAX ones in the
+      // general branch (C = 12, 20, 24, 96), the VEC = 1 forms fused them in the general branch and rounded xhat * b on its own
+      // in the aligned one -- so smsut_restail_bwd_amax differed from smsut_restail_bwd in the last bit of gy2 / gs, and the same
+      // tensor got other bits when the batch size moved it to the other branch.  (The shortcut's form is chosen once per unit,
+      // not per component: the loops below stay packed.)
+      float gz[VEC], ga[VEC];
 #pragma unroll
       for (int j = 0; j < VEC; ++j) {
         const float pre = remask ? in_affine(y[j], p.m2[j], p.r2[j], p.g2[j], p.be2[j]) + in_affine(sv[j], p.msv[j], p.rsv[j], p.gsv[j], p.bes[j])
                                  : o[j];
-        const float gz = g[j] * lrelu_mask(pre, slope);
-        const float a = p.av[j];
-        o1[j] = p.g2[j] * p.r2[j] * (gz - a - ((y[j] - p.m2[j]) * p.r2[j]) * p.b2v[j]);
-        o2[j] = t.ms ? p.gsv[j] * p.rsv[j] * (gz - a - ((sv[j] - p.msv[j]) * p.rsv[j]) * p.bsv[j]) : gz;
-        if constexpr (AMAX) { mx1 = fmaxf(mx1, fabsf(o1[j])); mx2 = fmaxf(mx2, fabsf(o2[j])); }
+        const float mk = lrelu_mask(pre, slope);
+        gz[j] = g[j] * mk;
+        ga[j] = __fmaf_rn(g[j], mk, -p.av[j]);
+        o1[j] = p.g2[j] * p.r2[j] * __fmaf_rn(-((y[j] - p.m2[j]) * p.r2[j]), p.b2v[j], ga[j]);
+      }
+      if (t.ms) {
+#pragma unroll
+        for (int j = 0; j < VEC; ++j) o2[j] = p.gsv[j] * p.rsv[j] * __fmaf_rn(-((sv[j] - p.msv[j]) * p.rsv[j]), p.bsv[j], ga[j]);
+      } else {
+#pragma unroll
+        for (int j = 0; j < VEC; ++j) o2[j] = gz[j];
+      }
+      if constexpr (AMAX) {
+#pragma unroll
+        for (int j = 0; j < VEC; ++j) { mx1 = fmaxf(mx1, fabsf(o1[j])); mx2 = fmaxf(mx2, fabsf(o2[j])); }
       }
       if constexpr (VEC == 4) { *(float4*)(gy2 + i * 4) = *(float4*)o1; *(float4*)(gs + i * 4) = *(float4*)o2; }
       else { gy2[i] = o1[0]; gs[i] = o2[0]; }
@@ -906,6 +923,7 @@ int smsut_in_slabs(int N, int HW, int C) {
 int smsut_instnorm_fwd(const float* x, const float* gamma, const float* beta, float* y, float* mean, float* rstd,
                        float* workspace, int N, int HW, int C, float eps, float slope, int has_act, void* stream) {
   SMSUT_REQUIRE(x && gamma && beta && y && mean && rstd && workspace && N > 0 && HW > 0 && C > 0);
+  SMSUT_REQUIRE((int64_t)HW * C < (1ll << 31));       // per-image walks index in 32 bits
   hipStream_t st = (hipStream_t)stream;
   const int ppc = pick_chunk(HW, C, N);
   const int chunks = (int)cdiv64(HW, ppc);
@@ -917,7 +935,6 @@ int smsut_instnorm_fwd(const float* x, const float* gamma, const float* beta, fl
     in_moments_partial<0, 1><<<g, TPB, 0, st>>>(x, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, workspace, HW, C, ppc, slope, fin);
   if (!fin.o0) in_moments_final<0><<<dim3((C + 15) / 16, N), TPB, 0, st>>>(workspace, chunks, C, HW, eps, mean, rstd, nullptr);
   const int64_t total = (int64_t)N * HW * C;
-  SMSUT_REQUIRE((int64_t)HW * C < (1ll << 31));       // per-image walks index in 32 bits
   if (C % 4 == 0)
     in_apply_fwd<4><<<img_grid((int64_t)HW * (C / 4), N), TPB, 0, st>>>(x, mean, rstd, gamma, beta, y, HW, C, slope, has_act);
   else
@@ -932,10 +949,10 @@ static int instnorm_fwd_partials_launch(const float* x, const float* gamma, cons
                                         float* rstd, const float* partials, int chunks, int N, int HW, int C, float eps,
                                         float slope, int has_act, void* stream, int hs) {
   SMSUT_REQUIRE(x && gamma && beta && y && mean && rstd && partials && chunks > 0 && N > 0 && HW > 0 && C > 0);
+  SMSUT_REQUIRE((int64_t)HW * C < (1ll << 31));       // per-image walks index in 32 bits
   hipStream_t st = (hipStream_t)stream;
   in_moments_final<0><<<dim3((C + 15) / 16, N), TPB, 0, st>>>(partials, chunks, C, HW, eps, mean, rstd, nullptr);
   const int64_t total = (int64_t)N * HW * C;
-  SMSUT_REQUIRE((int64_t)HW * C < (1ll << 31));       // per-image walks index in 32 bits
   if (hs == 2)
     in_apply_fwd<4, true, true><<<img_grid((int64_t)HW * (C / 4), N), TPB, 0, st>>>(x, mean, rstd, gamma, beta, y, HW, C, slope, has_act);
   else if (hs)
@@ -975,6 +992,7 @@ int smsut_instnorm_bwd(const float* gy, const float* x, const float* beta, const
                        const float* gamma, float* gx, float* a_mean, float* b_mean, float* ggamma, float* gbeta,
                        float* workspace, int N, int HW, int C, float slope, void* stream) {
   SMSUT_REQUIRE(gy && x && mean && rstd && gamma && gx && a_mean && b_mean && workspace && N > 0 && HW > 0 && C > 0);
+  SMSUT_REQUIRE((int64_t)HW * C < (1ll << 31));       // per-image walks index in 32 bits
   hipStream_t st = (hipStream_t)stream;
   const int ppc = pick_chunk(HW, C, N);
   const int chunks = (int)cdiv64(HW, ppc);
@@ -987,7 +1005,6 @@ int smsut_instnorm_bwd(const float* gy, const float* x, const float* beta, const
   if (!fin.o0) in_moments_final<1><<<dim3((C + 15) / 16, N), TPB, 0, st>>>(workspace, chunks, C, HW, 0.f, a_mean, b_mean, nullptr);
   float* gg = (ggamma && gbeta) ? ggamma : nullptr;       // affine gradients: computed by block 0 of the apply kernel
   const int64_t total = (int64_t)N * HW * C;
-  SMSUT_REQUIRE((int64_t)HW * C < (1ll << 31));       // per-image walks index in 32 bits
   if (C % 4 == 0)
     in_apply_bwd<4><<<img_grid((int64_t)HW * (C / 4), N), TPB, 0, st>>>(gy, x, beta, mean, rstd, gamma, a_mean, b_mean, gx, HW, C, slope,
                                                         N, gg, gbeta);
@@ -1021,7 +1038,7 @@ int smsut_instnorm_pool_bwd(const float* gyp, const float* x, const float* beta,
                             const float* gamma, float* gx, float* a_mean, float* b_mean, float* ggamma, float* gbeta,
                             float* workspace, int N, int H, int W, int C, float slope, void* stream) {
   SMSUT_REQUIRE(gyp && x && beta && mean && rstd && gamma && gx && a_mean && b_mean && workspace && N > 0 && H > 0 && W > 0 && C > 0 &&
-                !(H & 1) && !(W & 1));
+                !(H & 1) && !(W & 1) && (int64_t)H * W * C < (1ll << 31));
   hipStream_t st = (hipStream_t)stream;
   const int HW = H * W;
   const int ppc = pick_chunk(HW, C, N);
@@ -1034,7 +1051,6 @@ int smsut_instnorm_pool_bwd(const float* gyp, const float* x, const float* beta,
     in_moments_partial<1, 1, true><<<g, TPB, 0, st>>>(gyp, x, nullptr, gamma, beta, mean, rstd, workspace, HW, C, ppc, slope, fin, W);
   if (!fin.o0) in_moments_final<1><<<dim3((C + 15) / 16, N), TPB, 0, st>>>(workspace, chunks, C, HW, 0.f, a_mean, b_mean, nullptr);
   float* gg = (ggamma && gbeta) ? ggamma : nullptr;
-  SMSUT_REQUIRE((int64_t)HW * C < (1ll << 31));       // per-image walks index in 32 bits
   if (C % 4 == 0)
     in_apply_bwd<4, false, false, true><<<img_grid((int64_t)HW * (C / 4), N), TPB, 0, st>>>(gyp, x, beta, mean, rstd, gamma, a_mean, b_mean,
                                                                                          gx, HW, C, slope, N, gg, gbeta, nullptr, W);
@@ -1053,6 +1069,7 @@ int smsut_instnorm_bwd2(const float* v, const float* ug, const float* ub, const 
                         float* workspace, float* scratch, int N, int HW, int C, float slope, void* stream) {
   SMSUT_REQUIRE(v && gy && x && mean && rstd && gamma && a_mean && b_mean && d_gy && d_x && d_gamma && workspace &&
                 scratch && N > 0 && HW > 0 && C > 0);
+  SMSUT_REQUIRE((int64_t)HW * C < (1ll << 31));       // per-image walks index in 32 bits
   hipStream_t st = (hipStream_t)stream;
   const int ppc = pick_chunk(HW, C, N);
   const int chunks = (int)cdiv64(HW, ppc);
@@ -1066,7 +1083,6 @@ int smsut_instnorm_bwd2(const float* v, const float* ug, const float* ub, const 
   if (!fin.o0) in_moments_final<2><<<dim3((C + 15) / 16, N), TPB, 0, st>>>(workspace, chunks, C, HW, 0.f, cvm, dvm, em);
   in_bwd2_gamma<<<(C + 63) / 64, 64, 0, st>>>(rstd, a_mean, b_mean, cvm, dvm, em, N, C, HW, d_gamma);
   const int64_t total = (int64_t)N * HW * C;
-  SMSUT_REQUIRE((int64_t)HW * C < (1ll << 31));       // per-image walks index in 32 bits
   if (C % 4 == 0)
     in_apply_bwd2<4><<<ew_grid(total / 4), TPB, 0, st>>>(v, x, gy, beta, mean, rstd, gamma, a_mean, b_mean, cvm, dvm, em,
                                                           ug, ub, d_gy, d_x, total / 4, HW, C, slope);
@@ -1194,6 +1210,7 @@ static int restail_bwd_launch(const float* gout, const float* out, const float* 
                 workspace && N > 0 && HW > 0 && C > 0 && (!ms || (rs && gs_ && ggs && gbs)));
   // mr (r05): gout is the skip connection's gradient, the pooled path's is routed in while loading (two-IN tail, channel quads)
   SMSUT_REQUIRE(!mr || (mr->gp && mr->W > 0 && HW % mr->W == 0 && ms && b2 && bs && C % 4 == 0));
+  SMSUT_REQUIRE((int64_t)HW * C < (1ll << 31));       // per-image walks index in 32 bits
   const MaxRef mrv = mr ? *mr : MaxRef{nullptr, nullptr, 0};
   TailRef t{y2, m2, r2, g2, b2, s, ms, rs, gs_, bs};
   hipStream_t st = (hipStream_t)stream;
@@ -1224,7 +1241,6 @@ static int restail_bwd_launch(const float* gout, const float* out, const float* 
   if (!fin.o0 && !fin_in) in_moments_final<2><<<dim3((C + 15) / 16, N), TPB, 0, st>>>(workspace, chunks, C, HW, 0.f, a_mean, b2_mean, bs_mean);
   // the affine gradients (and the copy gbs = gb2) are written by block 0 of the apply kernel
   const int64_t total = (int64_t)N * HW * C;
-  SMSUT_REQUIRE((int64_t)HW * C < (1ll << 31));       // per-image walks index in 32 bits
 #define TAIL_APPLY(V, R, HSF, AM)                                                                                       \
   restail_bwd_apply<V, R, HSF, AM><<<img_grid((int64_t)HW * (C / V), N), TPB, 0, st>>>(gout, out, t, a_mean, b2_mean, bs_mean, gy2, gs, \
                                                                                HW, C, slope, N, gg2, gb2, ms ? ggs : nullptr,  \
@@ -1275,7 +1291,7 @@ int smsut_restail_bwd_pool(const float* gout, const float* gp, const void* idx, 
                            const float* bs, float* gy2, float* gs, float* a_mean, float* b2_mean, float* bs_mean, float* gg2,
                            float* gb2, float* ggs, float* gbs, float* workspace, int* tickets, float* amax, int N, int H, int W, int C,
                            float slope, int hs, void* stream) {
-  SMSUT_REQUIRE(gp && H > 0 && W > 0 && !(H & 1) && !(W & 1));
+  SMSUT_REQUIRE(gp && H > 0 && W > 0 && C > 0 && !(H & 1) && !(W & 1) && (int64_t)H * W * C < (1ll << 31));
   const MaxRef mr{gp, (const unsigned int*)idx, W};
   return restail_bwd_launch(gout, gout, (const float*)y2, m2, r2, g2, b2, (const float*)s, ms, rs, gs_, bs, gy2, gs, a_mean, b2_mean,
                             bs_mean, gg2, gb2, ggs, gbs, workspace, amax, N, H * W, C, slope, stream, hs != 0, tickets, &mr);

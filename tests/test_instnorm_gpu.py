@@ -18,6 +18,7 @@ import torch
 import torch.nn.functional as F
 
 from conftest import elem_rel_err, l2_rel, rel_err
+from norm_test_helpers import _check_guards, _poisoned, _tickets, aff32, gpu_mask
 
 pytestmark = pytest.mark.gpu
 
@@ -133,18 +134,6 @@ def fwd_stat_bounds(x64, K, eps):
 def ref_stats(x64, eps):
     m = x64.mean((2, 3))
     return m.numpy(), (1.0 / torch.sqrt(x64.var((2, 3), unbiased=False) + eps)).numpy()
-
-
-def gpu_mask(x, mean, rstd, g, b):
-    """The activation mask the kernels use: sign of in_affine(x, mean, rstd, gamma, beta) = fma(x - mean, rstd * gamma, beta) in
-    fp32 (common.h).  The fp32 difference and product are formed exactly as the kernel does; their product is exact in fp64, so the
-    sign of the fp64 sum is the sign of the fma.  (The fp64 reference then differentiates with THIS mask: a pre-activation within
-    an ulp of 0 must not flip between the two and move a, b by a whole gradient element.)"""
-    xn = x.numpy()
-    d = (xn - mean.cpu().numpy()[:, :, None, None]).astype(np.float32)
-    p = (rstd.cpu().numpy() * g.cpu().numpy()[None, :]).astype(np.float32)[:, :, None, None]
-    pre = d.astype(np.float64) * p + b.cpu().numpy().astype(np.float64)[None, :, None, None]
-    return torch.from_numpy(pre > 0)
 
 
 def ref_act(x64, g64, b64, eps, mask):
@@ -426,7 +415,6 @@ def test_offset_planes_within_the_derived_bound(ops, shape, ratio):
 
 
 # ---- 1e. in-launch finalize (FinRef, common.h) against fp64, on poisoned memory ------------------------------------------------
-SENT = 0x5A5A5A5A
 # (N, H, W): tiles per image 1 (and 1 with every workgroup walking several images), 2, 3, 5, 16, 17, 261 and 300 (> 256, not
 # multiples of 256) -- direct (H % 16 != 0) and resident-weight Winograd forms of the persistent kernel
 CONV_FIN_SHAPES = [("tiles_1", (256, 16, 16)), ("tiles_1_many_images", (1536, 16, 16)), ("tiles_2", (128, 16, 32)),
@@ -445,34 +433,11 @@ def conv_fin_cat(ci):
 # (N, HW, C) of the residual tail's backward: chunks per image 1, 2, 3, 5, 16, 17, 352
 TAIL_FIN_CASES = [("chunks_1", (2, 256, 32)), ("chunks_2", (2, 512, 32)), ("chunks_3", (3, 768, 32)), ("chunks_5", (2, 1280, 32)),
                   ("chunks_16", (2, 4096, 32)), ("chunks_17", (2, 4352, 32)), ("chunks_352", (1, 90000, 16))]
-GUARD_ROWS = 256            # the strided finalize addresses up to 255 rows past an image's block in its last round
-
-
-def _poisoned(n_floats, row_floats):
-    """a partial buffer of NaN with a NaN guard of GUARD_ROWS rows behind it; returns (buffer, guard view)"""
-    buf = torch.full((n_floats + GUARD_ROWS * row_floats,), float("nan"), device="cuda")
-    return buf, buf[n_floats:]
-
-
-def _tickets(n):
-    t = torch.full((n + 64,), SENT, dtype=torch.int32, device="cuda")
-    t[:n] = 0
-    return t
 
 
 def _outs(n, c, k):
     """k outputs [N][C], each followed by a sentinel guard (returns the base tensors)"""
     return [torch.full((n * c + 64,), 12345.0, device="cuda") for _ in range(k)]
-
-
-def _check_guards(parts, tickets, outs, n, c):
-    for g in parts:
-        assert torch.isnan(g).all(), "a partial was stored past the last image's block"
-    assert int(tickets[:n].abs().sum()) == 0, "tickets not zero again"
-    assert bool((tickets[n:] == SENT).all()), "the ticket guard was written"
-    for o in outs:
-        assert bool((o[n * c:] == 12345.0).all()), "an output was written past [N][C]"
-        assert torch.isfinite(o[:n * c]).all()
 
 
 def _nc(t, n, c):
@@ -644,11 +609,10 @@ def test_restail_bwd_fin_vs_fp64_on_poisoned_memory(ops, H, name, nhwc, shortcut
     # else the sign of `out`)
     y2c, m2c, r2c = y2.cpu(), m2.cpu(), r2.cpu()
     if shortcut:
-        def aff32(v, m, rr, g, b):
-            d = (v.numpy() - m.numpy()[:, None, :]).astype(np.float32)
-            p = (rr.numpy()[:, None, :] * g.cpu().numpy()[None, None, :]).astype(np.float32)
-            return (d.astype(np.float64) * p + b.cpu().numpy()[None, None, :]).astype(np.float32)      # fma, rounded once (to ~2^-29)
-        pre = aff32(y2c, m2c, r2c, g2, b2).astype(np.float64) + aff32(s.cpu(), ms.cpu(), rs.cpu(), gs_, bs)
+        def np_(v):
+            return v.cpu().numpy()
+        pre = (aff32(np_(y2c), np_(m2c), np_(r2c), np_(g2), np_(b2)).astype(np.float64) +
+               aff32(np_(s), np_(ms), np_(rs), np_(gs_), np_(bs)))
         mask = pre > 0
     else:
         mask = out.cpu().numpy() > 0
