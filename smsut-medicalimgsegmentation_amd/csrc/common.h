@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdlib.h>
+#include <type_traits>
 
 #define SMSUT_OK 0
 #define SMSUT_EINVAL (-1)
@@ -127,6 +128,66 @@ struct FinRef {
   float* o0; float* o1;          // [N][C]: (mean, rstd) of the forward statistics | (mean gz, mean gz * xhat) of the backward pair
   float* s0; float* s1;          // fused shortcut: the second statistics set's (mean, rstd); null otherwise
   float eps;
+};
+
+// ---- fused forms of the MFMA convs: kernel arguments (conv_mfma.hip, conv_wino.hip) --------------------------------------------
+// Input-side InstanceNorm + LeakyReLU (INAFF): the operand is lrelu(in_affine(x; mean[n,c], rstd[n,c], gamma[c], beta[c])).
+struct AffRef { const float* mean; const float* rstd; const float* gamma; const float* beta; float slope; };
+// Backward statistics (BST): the data-gradient is masked by the activation recomputed from y1 (fp16 when ConvCall::out_f16).
+struct BstRef { const float* y1; const float* mean; const float* rstd; const float* gamma; const float* beta; float slope; };
+// The block's 1x1 shortcut conv, fused: weights, result (fp16 when ConvCall::out_f16) and InstanceNorm partials.  With transposed
+// weights it is the fused shortcut DATA-gradient instead: w only, x2 = the shortcut's gradient.
+struct ScRef { const float* w; float* y; float* stats; };
+
+// The form of a conv_mfma_fwd_p / conv_wino_l instantiation as the launch sites name it: a set of these bits, one per bool template
+// parameter of the kernel (which documents the ones it has and static_asserts the combinations).
+enum : unsigned {
+  F_STATS = 1u << 0,    // InstanceNorm partials of the result
+  F_ACC = 1u << 1,      // result added to y
+  F_BST = 1u << 2,      // backward statistics (BstRef)
+  F_DUAL = 1u << 3,     // virtual-cat input [x, x2]
+  F_INAFF = 1u << 4,    // input-side InstanceNorm + LeakyReLU (AffRef)
+  F_F16 = 1u << 5,      // fp16 operands
+  F_K8 = 1u << 6,       // 8 reduction channels
+  F_SC = 1u << 7,       // fused 1x1 shortcut conv (ScRef)
+  F_SC2 = 1u << 8,      // fused shortcut data-gradient
+  F_N8 = 1u << 9,       // 8 result channels
+  F_WINO = 1u << 10,    // Winograd F(2x2,3x3) arithmetic, resident weights
+  F_O16 = 1u << 11,     // fp16 result storage (or fp16 y1 of the BST form)
+  F_I16 = 1u << 12,     // fp16 input storage
+  F_FIN = 1u << 13,     // statistics finalised inside the launch (FinRef)
+  F_PRE = 1u << 14,     // conv_wino_l: prepared weight image
+};
+// ... and a mask as a value, for the launchers' generic lambdas: go(Form<F_STATS | F_SC>{}, lds)
+template <unsigned F> using Form = std::integral_constant<unsigned, F>;
+
+// ---- one description of a conv launch, from the C-ABI entry points down to the launchers -------------------------------------------
+// Forward: x [N,H,W,Kdim], w [KS*KS][Kdim][Ndim] -> y [N,H,W,Ndim].  Every field but the operands, the shape and the stream is an
+// optional form; the launchers return -1 ("nothing launched") for a combination they do not have.
+struct ConvCall {
+  const void* x = nullptr;                // fp16 when in_f16
+  const float* x2 = nullptr;              // the input is the virtual cat([x, x2]) of two Kdim/2-channel tensors (or see ScRef)
+  const float* w = nullptr;
+  const float* wu = nullptr;              // caller's prepared Winograd image of w for this form (smsut_wino_prepare); null = on the fly
+  void* y = nullptr;                      // fp16 when out_f16 (statistics forms)
+  float* y2 = nullptr;                    // split output: result channels [0, split) go to y, the rest to y2
+  int split = 0;
+  int N = 0, H = 0, W = 0, Kdim = 0, Ndim = 0;
+  bool transposed_w = false;              // weights read transposed + tap-flipped: the data-gradient
+  bool accumulate = false;                // the result is ADDED to what y holds
+  bool f16_operands = false;              // operands rounded to fp16 while staged
+  bool in_f16 = false, out_f16 = false;   // half storage: x | y (and sc->y), or bst->y1 of the BST form
+  float* stats = nullptr;                 // InstanceNorm partials of y [N][tiles][Ndim][2]
+  const float* gsc = nullptr;             // fp16 operands: {s, 1/s} of a gradient input
+  const BstRef* bst = nullptr;
+  const AffRef* aff = nullptr;
+  const ScRef* sc = nullptr;
+  const FinRef* fin = nullptr;            // statistics finalised inside the launch (above)
+  int isc = 1, osc = 1, G = 1, ntap_out = 1;   // per-tile kernel only: input / output pixel stride, groups, output taps (convT 2x2)
+  hipStream_t stream = nullptr;
+  int* tiles_out = nullptr;               // planning query: only report the statistics tiles per image, launch nothing
+  // the `transposed` argument of conv_mfma_fwd / conv_wino_l: bit 0 = transposed_w, bit 1 = accumulate
+  int transposed_bits() const { return (transposed_w ? 1 : 0) | (accumulate ? 2 : 0); }
 };
 
 typedef unsigned long long smsut_u64;

@@ -415,14 +415,10 @@ conv_mfma_fwd(const float* __restrict__ x, const float* __restrict__ w, float* _
 // Input-side InstanceNorm + LeakyReLU ("INAFF"): the conv input is a = lrelu(in_affine(x; mean[n,c], rstd[n,c], gamma[c],
 // beta[c])) of the tensor actually read -- conv2 of a BasicBlock and its weight gradient read the raw conv1 output y1 and
 // normalise it while staging, so a1 is never written to or read from HBM.  Same in_affine() fma as norm.hip: same bits.
-struct AffRef { const float* mean; const float* rstd; const float* gamma; const float* beta; float slope; };
+// (AffRef, BstRef and ScRef, the kernel arguments of these forms: common.h)
 __device__ __forceinline__ float aff1(float v, float m, float r, float g, float b, float slope) {
   return lrelu_f(in_affine(v, m, r, g, b), slope);
 }
-
-struct BstRef { const float* y1; const float* mean; const float* rstd; const float* gamma; const float* beta; float slope; };
-
-struct ScRef { const float* w; float* y; float* stats; };   // SC: the block's 1x1 shortcut conv, fused (see conv_mfma_fwd_p)
 
 // Pixel stride (floats) of the staged input tile of the Winograd form: 20 = 5 x 16 B.  A lane of the transform reads the
 // channel quad kq of pixel (2*tc + b, 2*tr + a) of its 4x4 window; 16-byte slots (pixel * 5 + kq) mod 16 over the 16 tiles of
@@ -1938,39 +1934,35 @@ inline void launch_sum_splits(const float* part, float* out, int wsize, int spli
 }
 
 template <int KS, int TH, int WM, int WN, int NTN, int MW = TW>
-int launch_fwd(const float* x, const float* w, float* y, int N, int H, int W, int Kdim, int Ndim, int transposed,
-               int isc, int osc, int G, int ntap_out, hipStream_t st, float* stats = nullptr, int* tiles_out = nullptr,
-               const float* x2 = nullptr, float* y2 = nullptr, int split = 0, bool f16 = false, const float* gsc = nullptr) {
+int launch_fwd(const ConvCall& c) {
   constexpr int IH = TH + KS - 1, IW = MW + KS - 1;
   constexpr size_t sh16 = (size_t)(IH * IW * SPIX + KS * KS * CK * 16 * NTN) * sizeof(float);
   // (fp16 operands in 32-channel passes: the weight image [taps][16 NTN][40 halves] starts where the fp32 one would)
   constexpr size_t sh32 = (size_t)(IH * IW * SPIX) * sizeof(float) + (size_t)(KS * KS * 16 * NTN * 40) * sizeof(_Float16);
   constexpr size_t sh = sh16;
   static_assert(sh16 <= 64 * 1024 && (KS != 3 || MW != TW || sh32 <= 64 * 1024), "LDS budget");
-  const int tiles_x = (W + MW - 1) / MW, tiles_y = (H + TH - 1) / TH;
-  if (MW != TW && (isc != 1 || osc != 1 || G != 1 || ntap_out != 1)) return -1;
-  const int nz = (Ndim + 16 * NTN - 1) / (16 * NTN);
-  if (tiles_out) { *tiles_out = tiles_x * tiles_y; return 0; }          // planning query only
-  dim3 grid(tiles_x * tiles_y, N, nz * ntap_out);
-  if ((x2 && (isc != 1 || osc != 1 || G != 1 || ntap_out != 1 || (transposed & 1) || Kdim % 32 != 0)) ||
-      (y2 && (osc != 1 || ntap_out != 1 || stats || split <= 0 || split >= Ndim || split % 16 != 0)))
+  const int tiles_x = (c.W + MW - 1) / MW, tiles_y = (c.H + TH - 1) / TH;
+  const bool plain_taps = c.isc == 1 && c.osc == 1 && c.G == 1 && c.ntap_out == 1;
+  if (MW != TW && !plain_taps) return -1;
+  const int nz = (c.Ndim + 16 * NTN - 1) / (16 * NTN);
+  if (c.tiles_out) { *c.tiles_out = tiles_x * tiles_y; return 0; }          // planning query only
+  dim3 grid(tiles_x * tiles_y, c.N, nz * c.ntap_out);
+  if ((c.x2 && (!plain_taps || c.transposed_w || c.Kdim % 32 != 0)) ||
+      (c.y2 && (c.osc != 1 || c.ntap_out != 1 || c.stats || c.split <= 0 || c.split >= c.Ndim || c.split % 16 != 0)))
     return -1;
+  auto go = [&](auto kern, size_t lds) {             // (this kernel's operands are fp32 tensors)
+    kern<<<grid, TPB, lds, c.stream>>>((const float*)c.x, c.w, (float*)c.y, c.H, c.W, c.Kdim, c.Ndim, tiles_x, c.transposed_bits(), c.isc,
+                                       c.osc, c.G, nz, c.stats, c.x2, c.y2, c.split, c.gsc);
+    return 0;
+  };
   if constexpr (KS == 3 && MW == TW && SMSUT_F16_X32) {
     // 32-channel passes on every tile shape (config 5: 49.50 ms with 16-channel passes -> 48.56 ms, 48.95 with 32-channel passes on
     // the 16-row tiles only)
-    if (f16 && Kdim % 32 == 0 && Kdim >= 32 && (!x2 || (Kdim / 2) % 32 == 0) && isc == 1 && osc == 1 && G == 1) {
-      conv_mfma_fwd<KS, TH, WM, WN, NTN, true, MW, 32><<<grid, TPB, sh32, st>>>(x, w, y, H, W, Kdim, Ndim, tiles_x, transposed, isc,
-                                                                              osc, G, nz, stats, x2, y2, split, gsc);
-      return 0;
-    }
+    if (c.f16_operands && c.Kdim % 32 == 0 && c.Kdim >= 32 && (!c.x2 || (c.Kdim / 2) % 32 == 0) && c.isc == 1 && c.osc == 1 && c.G == 1)
+      return go(conv_mfma_fwd<KS, TH, WM, WN, NTN, true, MW, 32>, sh32);
   }
-  if (f16)
-    conv_mfma_fwd<KS, TH, WM, WN, NTN, true, MW><<<grid, TPB, sh, st>>>(x, w, y, H, W, Kdim, Ndim, tiles_x, transposed, isc,
-                                                                        osc, G, nz, stats, x2, y2, split, gsc);
-  else
-    conv_mfma_fwd<KS, TH, WM, WN, NTN, false, MW><<<grid, TPB, sh, st>>>(x, w, y, H, W, Kdim, Ndim, tiles_x, transposed, isc,
-                                                                         osc, G, nz, stats, x2, y2, split);
-  return 0;
+  if (c.f16_operands) return go(conv_mfma_fwd<KS, TH, WM, WN, NTN, true, MW>, sh);
+  return go(conv_mfma_fwd<KS, TH, WM, WN, NTN, false, MW>, sh);
 }
 
 // Persistent variant: LDS bytes and eligibility (see conv_mfma_fwd_p).
@@ -1994,17 +1986,25 @@ inline int p_occupancy(size_t lds) {
   return occ;
 }
 
+// Launch sites name a form by its F_* bits (common.h): fwd_p_kernel<KS, TH, NTN, NCH, F_STATS | F_SC | F_K8> is that instantiation
+// of conv_mfma_fwd_p.  The kernel's own parameter list stays one bool per flag, in this order: the roofline legs of bench.py and
+// profiles/summarize.py find a kernel in a trace by that list.
+template <int KS, int TH, int NTN, int NCH, unsigned F>
+constexpr auto fwd_p_kernel =
+    conv_mfma_fwd_p<KS, TH, NTN, NCH, (F & F_STATS) != 0, (F & F_ACC) != 0, (F & F_BST) != 0, (F & F_DUAL) != 0, (F & F_INAFF) != 0,
+                    (F & F_F16) != 0, (F & F_K8) != 0, (F & F_SC) != 0, (F & F_SC2) != 0, (F & F_N8) != 0, (F & F_WINO) != 0,
+                    (F & F_O16) != 0, (F & F_I16) != 0, (F & F_FIN) != 0>;
+
 template <int KS, int TH, int NTN, int NCH, bool K8 = false, bool N8 = false, bool WINO = false>
-int launch_fwd_p(const float* x, const float* w, float* y, int N, int H, int W, int Kdim, int Ndim, int transposed,
-                 hipStream_t st, float* stats = nullptr, int* tiles_out = nullptr, const BstRef* bst = nullptr,
-                 float* y2 = nullptr, int split = 0, const float* x2 = nullptr, const AffRef* aff = nullptr,
-                 bool f16 = false, const float* gsc = nullptr, const ScRef* sc = nullptr, int hs = 0, const FinRef* fin = nullptr) {
-  const bool o16 = (hs & 1) != 0, i16 = (hs & 2) != 0;
+int launch_fwd_p(const ConvCall& c) {
+  const bool tw = c.transposed_w, acc = c.accumulate, f16 = c.f16_operands, o16 = c.out_f16, i16 = c.in_f16;
+  const auto x2 = c.x2; const auto y2 = c.y2; const auto stats = c.stats;
+  const auto bst = c.bst; const auto aff = c.aff; const auto sc = c.sc; const auto fin = c.fin;
+  const int N = c.N, H = c.H, W = c.W, Kdim = c.Kdim, Ndim = c.Ndim, split = c.split;
   // in-launch finalize (FIN instantiations): fp32 statistics / BST forms of the fused block -- plain, input-side IN, fused shortcut
-  if (fin && (!fin->tickets || !fin->o0 || !fin->o1 || !stats || f16 || N8 || y2 || o16 || i16 || (transposed & 2) ||
-              (fin->s0 && !(sc && !(transposed & 1) && sc->stats && fin->s1)) || (!fin->s0 && sc)))
+  if (fin && (!fin->tickets || !fin->o0 || !fin->o1 || !stats || f16 || N8 || y2 || o16 || i16 || acc ||
+              (fin->s0 && !(sc && !tw && sc->stats && fin->s1)) || (!fin->s0 && sc)))
     return -1;
-  const FinRef finv = fin ? *fin : FinRef{};   // half storage: bit 0 = the result (or the BST y1) is fp16, bit 1 = the input is
   constexpr size_t sh = fwd_p_lds<KS, TH, NTN, NCH, WINO>();
   // fused 1x1 shortcut (SC): its weight block and a second statistics scratch
   constexpr size_t sh_sc = sh + (size_t)(16 * NCH * 16 * NTN + 2 * 4 * 16 * NTN * 2 + 8) * sizeof(float);
@@ -2013,26 +2013,26 @@ int launch_fwd_p(const float* x, const float* w, float* y, int N, int H, int W, 
   if (Kdim != (K8 ? 8 : 16 * NCH) || W % TW != 0 || H % TH != 0 || (N8 ? Ndim != 8 : Ndim % (16 * NTN) != 0) ||
       (int64_t)N * H * W * (Kdim > Ndim ? Kdim : Ndim) >= (1ll << 31))
     return -1;
-  if (N8 && (NTN != 1 || K8 || stats || tiles_out || bst || y2 || aff || f16 || !(transposed & 1) || (x2 && !(sc && sc->w)))) return -1;
+  if (N8 && (NTN != 1 || K8 || stats || c.tiles_out || bst || y2 || aff || f16 || !tw || (x2 && !(sc && sc->w)))) return -1;
   if (K8 && (f16 || bst || x2 || aff)) return -1;
   if (WINO && (f16 || K8 || N8)) return -1;                                    // Winograd form: fp32
   const int tiles_x = W / TW, tiles_y = H / TH;
   const int tiles_img = tiles_x * tiles_y;
   if (y2 && (split <= 0 || split >= Ndim || split % (16 * NTN) != 0 || stats || bst)) return -1;
-  if (x2 && !(sc && (transposed & 1)) && (NCH % 2 != 0 || !stats || bst || y2 || transposed)) return -1;   // virtual-cat input: forward statistics form
-  if (aff && (!stats || bst || y2 || x2 || transposed)) return -1;              // input-side IN: forward statistics form
-  const bool sc2 = sc && (transposed & 1);                                      // fused shortcut DATA-gradient (see SC2)
-  if (sc2 && (K8 || KS != 3 || NCH % 2 != 0 || !x2 || stats || bst || aff || (transposed & 2) || (f16 && (WINO || N8)) || !sc->w)) return -1;
-  if (sc && !sc2 && (KS != 3 || sh_sc > 64 * 1024 || !stats || bst || y2 || aff || transposed || !sc->w || !sc->y || !sc->stats ||
+  if (x2 && !(sc && tw) && (NCH % 2 != 0 || !stats || bst || y2 || tw || acc)) return -1;   // virtual-cat input: forward statistics form
+  if (aff && (!stats || bst || y2 || x2 || tw || acc)) return -1;                // input-side IN: forward statistics form
+  const bool sc2 = sc && tw;                                                    // fused shortcut DATA-gradient (see SC2)
+  if (sc2 && (K8 || KS != 3 || NCH % 2 != 0 || !x2 || stats || bst || aff || acc || (f16 && (WINO || N8)) || !sc->w)) return -1;
+  if (sc && !sc2 && (KS != 3 || sh_sc > 64 * 1024 || !stats || bst || y2 || aff || tw || acc || !sc->w || !sc->y || !sc->stats ||
                      (K8 && x2) || (f16 && (K8 || WINO))))
     return -1;                                                                  // fused shortcut: forward statistics forms
   if (i16 && (!o16 || bst || x2 || sc)) return -1;
-  if (o16 && !bst && (!(f16 || (K8 && sc)) || !stats || (aff && !i16) || y2 || transposed || (K8 && !sc) || N8 || WINO || KS != 3)) return -1;   // fp16 result storage
-  if (o16 && bst && (!f16 || !stats || aff || y2 || x2 || sc || (transposed & 2) || K8 || N8 || WINO || KS != 3)) return -1;  // fp16 y1 of the BST form
-  if (tiles_out) { *tiles_out = tiles_img; return 0; }
+  if (o16 && !bst && (!(f16 || (K8 && sc)) || !stats || (aff && !i16) || y2 || tw || acc || (K8 && !sc) || N8 || WINO || KS != 3)) return -1;   // fp16 result storage
+  if (o16 && bst && (!f16 || !stats || aff || y2 || x2 || sc || acc || K8 || N8 || WINO || KS != 3)) return -1;  // fp16 y1 of the BST form
+  if (c.tiles_out) { *c.tiles_out = tiles_img; return 0; }
   const int nz = N8 ? 1 : Ndim / (16 * NTN);
   // The persistent grid is sized for ONE resident round of the kernel instantiation ACTUALLY launched, at its own dynamic LDS size
-  // (P_K below; ADVICE r04: one occupancy figure -- the fp32 statistics form's -- used to serve every form of this template, whatever
+  // (go below; ADVICE r04: one occupancy figure -- the fp32 statistics form's -- used to serve every form of this template, whatever
   // its registers and LDS: fused shortcut, fp16 operands, half storage).
   const int64_t items = (int64_t)N * tiles_img;
   int ipw = 1;
@@ -2043,150 +2043,92 @@ int launch_fwd_p(const float* x, const float* w, float* y, int N, int H, int W, 
     if (ipw < 1) ipw = 1;
     grid.x = (unsigned)((items + ipw - 1) / ipw);
   };
-#define P_K(SH, ARGS, ...)                                  \
-  do {                                                      \
-    size_grid(p_occupancy<__VA_ARGS__>(SH));                \
-    __VA_ARGS__<<<grid, TPB, SH, st>>> ARGS;                \
-  } while (0)
-  const int tr = transposed & 1;
-  const BstRef bstv = bst ? *bst : BstRef{};
-  const AffRef affv = aff ? *aff : AffRef{};
-  // one launch site for every form; the fp16-operand twin of each form is chosen at run time (f16)
-#define P_GO(ST, AC, BS, DU, IA)                                                                                             \
-  do {                                                                                                                       \
-    if constexpr ((ST || BS) && !AC) {                                                                                       \
-      if (fin) {                                      /* the same form, finalising its statistics in the launch */          \
-        if constexpr (K8) {                                                                                                  \
-          if constexpr (!BS && !DU && !IA)                                                                                   \
-            P_K(sh, (x, w, y, N, H, W, Ndim, tiles_x, tiles_img, ipw, tr, stats, bstv, y2, split, x2, affv, nullptr, ScRef{}, finv), \
-                conv_mfma_fwd_p<KS, TH, NTN, NCH, ST, AC, false, false, false, false, true, false, false, false, false, false, false, true>); \
-        } else {                                                                                                             \
-          P_K(sh, (x, w, y, N, H, W, Ndim, tiles_x, tiles_img, ipw, tr, stats, bstv, y2, split, x2, affv, nullptr, ScRef{}, finv), \
-              conv_mfma_fwd_p<KS, TH, NTN, NCH, ST, AC, BS, DU, IA, false, false, false, false, false, WINO, false, false, true>); \
-        }                                                                                                                    \
-        break;                                                                                                               \
-      }                                                                                                                      \
-    }                                                                                                                        \
-    if constexpr (K8) {                                                                                                      \
-      if constexpr (!BS && !DU && !IA)                                                                                       \
-        P_K(sh, (x, w, y, N, H, W, Ndim, tiles_x, tiles_img, ipw, tr, stats, bstv, y2, split, x2, affv, nullptr), conv_mfma_fwd_p<KS, TH, NTN, NCH, ST, AC, false, false, false, false, true>);                 \
-    } else if constexpr (WINO) {                                                                                             \
-      P_K(sh, (x, w, y, N, H, W, Ndim, tiles_x, tiles_img, ipw, tr, stats, bstv, y2, split, x2, affv, nullptr), conv_mfma_fwd_p<KS, TH, NTN, NCH, ST, AC, BS, DU, IA, false, false, false, false, false, true>);                   \
-    } else if (f16)                                                                                                          \
-      P_K(sh, (x, w, y, N, H, W, Ndim, tiles_x, tiles_img, ipw, tr, stats, bstv, y2, split, x2, affv, gsc), conv_mfma_fwd_p<KS, TH, NTN, NCH, ST, AC, BS, DU, IA, true>);                       \
-    else                                                                                                                     \
-      P_K(sh, (x, w, y, N, H, W, Ndim, tiles_x, tiles_img, ipw, tr, stats, bstv, y2, split, x2, affv, nullptr), conv_mfma_fwd_p<KS, TH, NTN, NCH, ST, AC, BS, DU, IA, false>);                   \
-  } while (0)
+  // one launch site for every form.  The fp16 buffers of the half-storage forms (x, y) travel as the kernel's float pointers.
+  auto go = [&](auto form, size_t lds) {
+    constexpr auto kern = fwd_p_kernel<KS, TH, NTN, NCH, decltype(form)::value>;
+    size_grid(p_occupancy<kern>(lds));
+    kern<<<grid, TPB, lds, c.stream>>>((const float*)c.x, c.w, (float*)c.y, N, H, W, Ndim, tiles_x, tiles_img, ipw, tw ? 1 : 0, stats,
+                                       bst ? *bst : BstRef{}, y2, split, x2, aff ? *aff : AffRef{}, f16 ? c.gsc : nullptr,
+                                       sc ? *sc : ScRef{}, fin ? *fin : FinRef{});
+    return 0;
+  };
+  // `form`, with the bits of `extra` when `on`: a run-time twin, both of which this instantiation has
+  auto go_opt = [&](bool on, auto extra, auto form, size_t lds) {
+    return on ? go(Form<decltype(form)::value | decltype(extra)::value>{}, lds) : go(form, lds);
+  };
+  // the plain family (statistics, accumulate, BST, virtual cat, input-side IN) in this instantiation's arithmetic (K8 / WINO / direct),
+  // with the in-launch finalize or the fp16-operand twin chosen at run time
+  auto go_plain = [&](auto form) {
+    constexpr unsigned B = decltype(form)::value | (K8 ? F_K8 : 0u) | (WINO ? F_WINO : 0u);
+    if constexpr (K8 && (B & (F_BST | F_DUAL | F_INAFF)) != 0) return -1;
+    else {
+      if constexpr ((B & (F_STATS | F_BST)) != 0 && !(B & F_ACC)) {
+        if (fin) return go(Form<B | F_FIN>{}, sh);          // the same form, finalising its statistics in the launch
+      }
+      if constexpr (!K8 && !WINO) return go_opt(f16, Form<F_F16>{}, Form<B>{}, sh);
+      else return go(Form<B>{}, sh);
+    }
+  };
+  // (every `if constexpr` below ends in `else return -1`: a form this instantiation does not have must report
+  //  "nothing launched", never fall through to `return 0` with y / ysc / the statistics left unwritten)
   if constexpr (N8) {                           // 8 result channels: data-gradient forms only (checked above)
     if constexpr (NTN == 1 && !K8 && KS == 3) {
       if (sc2) {
-        if constexpr (NCH % 2 == 0)
-          P_K(sh, (x, w, y, N, H, W, Ndim, tiles_x, tiles_img, ipw, 1, nullptr, bstv, nullptr, 0, x2, affv, nullptr, *sc),
-              conv_mfma_fwd_p<KS, TH, NTN, NCH, false, false, false, true, false, false, false, false, true, true>);
+        if constexpr (NCH % 2 == 0) return go(Form<F_DUAL | F_SC2 | F_N8>{}, sh);
         else return -1;
-      } else if (transposed & 2)
-        P_K(sh, (x, w, y, N, H, W, Ndim, tiles_x, tiles_img, ipw, 1, nullptr, bstv, nullptr, 0, nullptr, affv, nullptr),
-            conv_mfma_fwd_p<KS, TH, NTN, NCH, false, true, false, false, false, false, false, false, false, true>);
-      else
-        P_K(sh, (x, w, y, N, H, W, Ndim, tiles_x, tiles_img, ipw, 1, nullptr, bstv, nullptr, 0, nullptr, affv, nullptr),
-            conv_mfma_fwd_p<KS, TH, NTN, NCH, false, false, false, false, false, false, false, false, false, true>);
-      return 0;
+      }
+      return go_opt(acc, Form<F_ACC>{}, Form<F_N8>{}, sh);
     } else return -1;
   } else if (sc2) {
-    // (every `if constexpr` below ends in `else return -1`: a form this instantiation does not have must report
-    //  "nothing launched", never fall through to `return 0` with y / ysc / the statistics left unwritten)
     if constexpr (!K8 && KS == 3 && NCH % 2 == 0) {
       if (f16) {
-        if constexpr (!WINO)
-          P_K(sh, (x, w, y, N, H, W, Ndim, tiles_x, tiles_img, ipw, 1, nullptr, bstv, y2, split, x2, affv, gsc, *sc),
-              conv_mfma_fwd_p<KS, TH, NTN, NCH, false, false, false, true, false, true, false, false, true>);
+        if constexpr (!WINO) return go(Form<F_DUAL | F_F16 | F_SC2>{}, sh);
         else return -1;
-      } else
-        P_K(sh, (x, w, y, N, H, W, Ndim, tiles_x, tiles_img, ipw, 1, nullptr, bstv, y2, split, x2, affv, nullptr, *sc),
-            conv_mfma_fwd_p<KS, TH, NTN, NCH, false, false, false, true, false, false, false, false, true, false, WINO>);
+      }
+      return go(Form<F_DUAL | F_SC2 | (WINO ? F_WINO : 0u)>{}, sh);
     } else return -1;
   } else if (sc) {
     if constexpr (K8 && KS == 3 && sh_sc <= 64 * 1024) {
-      if (o16)
-        P_K(sh_sc, (x, w, y, N, H, W, Ndim, tiles_x, tiles_img, ipw, 0, stats, bstv, nullptr, 0, nullptr, affv, nullptr, *sc),
-            conv_mfma_fwd_p<KS, TH, NTN, NCH, true, false, false, false, false, false, true, true, false, false, false, true>);
-      else if (fin)
-        P_K(sh_sc, (x, w, y, N, H, W, Ndim, tiles_x, tiles_img, ipw, 0, stats, bstv, nullptr, 0, nullptr, affv, nullptr, *sc, finv),
-            conv_mfma_fwd_p<KS, TH, NTN, NCH, true, false, false, false, false, false, true, true, false, false, false, false, false, true>);
-      else
-        P_K(sh_sc, (x, w, y, N, H, W, Ndim, tiles_x, tiles_img, ipw, 0, stats, bstv, nullptr, 0, nullptr, affv, nullptr, *sc),
-            conv_mfma_fwd_p<KS, TH, NTN, NCH, true, false, false, false, false, false, true, true>);
+      if (o16) return go(Form<F_STATS | F_K8 | F_SC | F_O16>{}, sh_sc);
+      return go_opt(fin != nullptr, Form<F_FIN>{}, Form<F_STATS | F_K8 | F_SC>{}, sh_sc);
     } else if constexpr (!K8 && KS == 3 && sh_sc <= 64 * 1024) {
       if (f16) {                                   // fp16 operands (config 5; r04): direct form, plain or virtual-cat input
         if constexpr (!WINO) {
-#define SC16_GO(DU, O)                                                                                                        \
-  P_K(sh_sc, (x, w, y, N, H, W, Ndim, tiles_x, tiles_img, ipw, 0, stats, bstv, nullptr, 0, x2, affv, nullptr, *sc),           \
-      conv_mfma_fwd_p<KS, TH, NTN, NCH, true, false, false, DU, false, true, false, true, false, false, false, O>)
-          if (x2) {
-            if constexpr (NCH % 2 == 0) { if (o16) SC16_GO(true, true); else SC16_GO(true, false); }
-            else return -1;
-          } else {
-            if (o16) SC16_GO(false, true); else SC16_GO(false, false);
-          }
-#undef SC16_GO
+          if (!x2) return go_opt(o16, Form<F_O16>{}, Form<F_STATS | F_F16 | F_SC>{}, sh_sc);
+          if constexpr (NCH % 2 == 0) return go_opt(o16, Form<F_O16>{}, Form<F_STATS | F_DUAL | F_F16 | F_SC>{}, sh_sc);
+          else return -1;
         } else return -1;
-      } else if (x2) {
-        if constexpr (NCH % 2 == 0) {
-          if (fin)
-            P_K(sh_sc, (x, w, y, N, H, W, Ndim, tiles_x, tiles_img, ipw, 0, stats, bstv, nullptr, 0, x2, affv, nullptr, *sc, finv),
-                conv_mfma_fwd_p<KS, TH, NTN, NCH, true, false, false, true, false, false, false, true, false, false, WINO, false, false, true>);
-          else
-            P_K(sh_sc, (x, w, y, N, H, W, Ndim, tiles_x, tiles_img, ipw, 0, stats, bstv, nullptr, 0, x2, affv, nullptr, *sc),
-                conv_mfma_fwd_p<KS, TH, NTN, NCH, true, false, false, true, false, false, false, true, false, false, WINO>);
-        } else return -1;
-      } else if (fin) {
-        P_K(sh_sc, (x, w, y, N, H, W, Ndim, tiles_x, tiles_img, ipw, 0, stats, bstv, nullptr, 0, nullptr, affv, nullptr, *sc, finv),
-            conv_mfma_fwd_p<KS, TH, NTN, NCH, true, false, false, false, false, false, false, true, false, false, WINO, false, false, true>);
-      } else {
-        P_K(sh_sc, (x, w, y, N, H, W, Ndim, tiles_x, tiles_img, ipw, 0, stats, bstv, nullptr, 0, nullptr, affv, nullptr, *sc),
-            conv_mfma_fwd_p<KS, TH, NTN, NCH, true, false, false, false, false, false, false, true, false, false, WINO>);
       }
+      constexpr unsigned SCW = F_STATS | F_SC | (WINO ? F_WINO : 0u);
+      if (!x2) return go_opt(fin != nullptr, Form<F_FIN>{}, Form<SCW>{}, sh_sc);
+      if constexpr (NCH % 2 == 0) return go_opt(fin != nullptr, Form<F_FIN>{}, Form<SCW | F_DUAL>{}, sh_sc);
+      else return -1;
     } else return -1;
   } else if (aff && i16) {                        // fp16 y1 in, normalised while staged, fp16 y2 out (half-storage conv2)
-    if constexpr (!K8 && !WINO && KS == 3)
-      P_K(sh, (x, w, y, N, H, W, Ndim, tiles_x, tiles_img, ipw, 0, stats, bstv, nullptr, 0, nullptr, affv, nullptr),
-          conv_mfma_fwd_p<KS, TH, NTN, NCH, true, false, false, false, true, true, false, false, false, false, false, true, true>);
+    if constexpr (!K8 && !WINO && KS == 3) return go(Form<F_STATS | F_INAFF | F_F16 | F_O16 | F_I16>{}, sh);
     else return -1;
   } else if (aff) {
-    P_GO(true, false, false, false, true);
+    return go_plain(Form<F_STATS | F_INAFF>{});
   } else if (o16 && !bst) {                       // fp16 operands, fp16 result storage: plain or virtual-cat forward statistics form
     if constexpr (!K8 && !WINO && KS == 3) {
-      if (x2) {
-        if constexpr (NCH % 2 == 0)
-          P_K(sh, (x, w, y, N, H, W, Ndim, tiles_x, tiles_img, ipw, 0, stats, bstv, nullptr, 0, x2, affv, nullptr),
-              conv_mfma_fwd_p<KS, TH, NTN, NCH, true, false, false, true, false, true, false, false, false, false, false, true>);
-        else return -1;
-      } else if (i16)
-        P_K(sh, (x, w, y, N, H, W, Ndim, tiles_x, tiles_img, ipw, 0, stats, bstv, nullptr, 0, nullptr, affv, nullptr),
-            conv_mfma_fwd_p<KS, TH, NTN, NCH, true, false, false, false, false, true, false, false, false, false, false, true, true>);
-      else
-        P_K(sh, (x, w, y, N, H, W, Ndim, tiles_x, tiles_img, ipw, 0, stats, bstv, nullptr, 0, nullptr, affv, nullptr),
-            conv_mfma_fwd_p<KS, TH, NTN, NCH, true, false, false, false, false, true, false, false, false, false, false, true>);
+      if (!x2) return go_opt(i16, Form<F_I16>{}, Form<F_STATS | F_F16 | F_O16>{}, sh);
+      if constexpr (NCH % 2 == 0) return go(Form<F_STATS | F_DUAL | F_F16 | F_O16>{}, sh);
+      else return -1;
     } else return -1;
   } else if (x2) {
-    if constexpr (NCH % 2 == 0) P_GO(true, false, false, true, false);
+    if constexpr (NCH % 2 == 0) return go_plain(Form<F_STATS | F_DUAL>{});
     else return -1;
   } else if (bst && o16) {
-    if constexpr (!K8 && !WINO && KS == 3)
-      P_K(sh, (x, w, y, N, H, W, Ndim, tiles_x, tiles_img, ipw, tr, stats, bstv, nullptr, 0, nullptr, affv, gsc),
-          conv_mfma_fwd_p<KS, TH, NTN, NCH, false, false, true, false, false, true, false, false, false, false, false, true>);
+    if constexpr (!K8 && !WINO && KS == 3) return go(Form<F_BST | F_F16 | F_O16>{}, sh);
     else return -1;
   } else if (bst) {
-    if (!stats || (transposed & 2)) return -1;
-    P_GO(false, false, true, false, false);
-  } else if (transposed & 2) {
+    if (!stats || acc) return -1;
+    return go_plain(Form<F_BST>{});
+  } else if (acc) {
     if (stats) return -1;
-    P_GO(false, true, false, false, false);
-  } else if (stats) P_GO(true, false, false, false, false);
-  else P_GO(false, false, false, false, false);
-#undef P_GO
-#undef P_K
-  return 0;
+    return go_plain(Form<F_ACC>{});
+  } else if (stats) return go_plain(Form<F_STATS>{});
+  else return go_plain(Form<0u>{});
   }
 }
 
@@ -2211,43 +2153,33 @@ inline bool fwd_any_eligible(int N, int H, int W, int Kdim, int Ndim, bool f16) 
 // 16->16, 103 vs 88 at 128^2 16->32), 32-channel reductions ~8 % faster with 32 output channels per workgroup when
 // Ndim allows it (120 vs 111 TF at 128^2 32->32).  ONE selector for the plain, statistics, accumulate and BST forms,
 // so that smsut_conv2d_mfma_tiles() always describes the partials the launched variant writes.
-inline int select_fwd_p(const float* x, const float* w, float* y, int N, int H, int W, int Kdim, int Ndim, int transposed,
-                        hipStream_t st, float* stats, int* tiles_out, const BstRef* bst, float* y2 = nullptr, int split = 0,
-                        const float* x2 = nullptr, const AffRef* aff = nullptr, bool f16 = false, const float* gsc = nullptr,
-                        const ScRef* sc = nullptr, const float* wu = nullptr, int hs = 0, const FinRef* fin = nullptr) {
-#define PARGS x, w, y, N, H, W, Kdim, Ndim, transposed, st, stats, tiles_out, bst, y2, split, x2, aff, f16, gsc, sc, hs, fin
+inline int select_fwd_p(const ConvCall& c) {
+  const int N = c.N, H = c.H, W = c.W, Kdim = c.Kdim, Ndim = c.Ndim;
+  const bool f16 = c.f16_operands;
   // (the fused shortcut data-gradient at 64 reduction channels stays on the direct resident-weight form: 107 us vs 142 us at
   //  16 x 128^2 (32 + 32) -> 64 -- its second-half chunks are a run-time branch inside the staging parts, r03 notes)
-  const bool sc2_64 = sc && (transposed & 1) && Kdim == 64 && fwd_p_eligible(N, H, W, Kdim, Ndim);
-  if (!f16 && !sc2_64 && wino_l_shape(N, H, W, Kdim, Ndim)) {         // Winograd, streamed weights (conv_wino.hip): every fp32 form
-    WinoBst wb; WinoAff wa; WinoSc ws;
-    if (bst) wb = WinoBst{bst->y1, bst->mean, bst->rstd, bst->gamma, bst->beta, bst->slope};
-    if (aff) wa = WinoAff{aff->mean, aff->rstd, aff->gamma, aff->beta, aff->slope};
-    if (sc) ws = WinoSc{sc->w, sc->y, sc->stats};
-    return smsut_wino_l_launch(x, x2, w, y, y2, split, N, H, W, Kdim, Ndim, transposed, stats, tiles_out, bst ? &wb : nullptr,
-                               aff ? &wa : nullptr, sc ? &ws : nullptr, st, wu, fin);
-  }
+  const bool sc2_64 = c.sc && c.transposed_w && Kdim == 64 && fwd_p_eligible(N, H, W, Kdim, Ndim);
+  if (!f16 && !sc2_64 && wino_l_shape(N, H, W, Kdim, Ndim)) return smsut_wino_l_launch(c);   // Winograd, streamed weights (conv_wino.hip): every fp32 form
   if (Ndim == 8) {                                   // 8 result channels (see conv_mfma_fwd_p, N8): data-gradient forms
-    if (Kdim == 16) return (H % 16 == 0) ? launch_fwd_p<3, 16, 1, 1, false, true>(PARGS) : launch_fwd_p<3, 8, 1, 1, false, true>(PARGS);
-    if (Kdim == 32) return launch_fwd_p<3, 8, 1, 2, false, true>(PARGS);   // (16-row items measured no better: 8.89 vs 8.91 ms U-Net)
+    if (Kdim == 16) return (H % 16 == 0) ? launch_fwd_p<3, 16, 1, 1, false, true>(c) : launch_fwd_p<3, 8, 1, 1, false, true>(c);
+    if (Kdim == 32) return launch_fwd_p<3, 8, 1, 2, false, true>(c);   // (16-row items measured no better: 8.89 vs 8.91 ms U-Net)
     return -1;
   }
-  if (Kdim == 8) return (H % 16 == 0) ? launch_fwd_p<3, 16, 1, 1, true>(PARGS) : launch_fwd_p<3, 8, 1, 1, true>(PARGS);
+  if (Kdim == 8) return (H % 16 == 0) ? launch_fwd_p<3, 16, 1, 1, true>(c) : launch_fwd_p<3, 8, 1, 1, true>(c);
   // Winograd F(2x2,3x3) form (r03: 1.2-1.4x the direct form on these shapes, scratch/wino_probe.py): every fp32 form of the
   // 16- and 32-channel reductions on 16-row items (winograd_on(): the direct forms are the reference).  Chosen by SHAPE only,
   // never by form, so that the forms of one shape stay bit-identical to each other (virtual cat vs materialised, fused shortcut vs
   // plain, input-side IN vs applied).
   if (winograd_on() && !f16 && H % 16 == 0 && (Kdim == 16 || Kdim == 32))
-    return Kdim == 16 ? launch_fwd_p<3, 16, 1, 1, false, false, true>(PARGS) : launch_fwd_p<3, 16, 1, 2, false, false, true>(PARGS);
-  if (Kdim == 16 && H % 16 == 0) return launch_fwd_p<3, 16, 1, 1>(PARGS);
+    return Kdim == 16 ? launch_fwd_p<3, 16, 1, 1, false, false, true>(c) : launch_fwd_p<3, 16, 1, 2, false, false, true>(c);
+  if (Kdim == 16 && H % 16 == 0) return launch_fwd_p<3, 16, 1, 1>(c);
   // (fp16 operands, Kdim 32 stay on 8-row items: 16-row items re-read 1.27x their input as halo instead of 1.41x, but the halo rows
   //  are L2 hits under the XCD-aware item map -- config 5 measured 52.77 ms on 8-row items, 52.80 with 16-row items for Ndim 16 only,
   //  53.59 with them on every Kdim-32 shape)
-  if (Kdim == 32 && Ndim % 32 == 0 && !(y2 && split % 32 != 0)) return launch_fwd_p<3, 8, 2, 2>(PARGS);   // (32-channel slabs must not straddle a split)
-  if (Kdim == 16) return launch_fwd_p<3, 8, 1, 1>(PARGS);
-  if (Kdim == 32) return launch_fwd_p<3, 8, 1, 2>(PARGS);
-  if (Kdim == 64) return launch_fwd_p<3, 8, 1, 4>(PARGS);
-#undef PARGS
+  if (Kdim == 32 && Ndim % 32 == 0 && !(c.y2 && c.split % 32 != 0)) return launch_fwd_p<3, 8, 2, 2>(c);   // (32-channel slabs must not straddle a split)
+  if (Kdim == 16) return launch_fwd_p<3, 8, 1, 1>(c);
+  if (Kdim == 32) return launch_fwd_p<3, 8, 1, 2>(c);
+  if (Kdim == 64) return launch_fwd_p<3, 8, 1, 4>(c);
   return -1;
 }
 
@@ -2258,88 +2190,77 @@ inline bool fwd_p_n8_eligible(int N, int H, int W, int Kdim, int Ndim) {
 }
 
 template <int KS>
-int dispatch_fwd(const float* x, const float* w, float* y, int N, int H, int W, int Kdim, int Ndim, int transposed,
-                 int isc, int osc, int G, int ntap_out, hipStream_t st, float* stats = nullptr, int* tiles_out = nullptr,
-                 const float* x2 = nullptr, float* y2 = nullptr, int split = 0, bool f16 = false, const float* gsc = nullptr,
-                 const float* wu = nullptr) {
-#define ARGS x, w, y, N, H, W, Kdim, Ndim, transposed, isc, osc, G, ntap_out, st, stats, tiles_out, x2, y2, split, f16, gsc
+int dispatch_fwd(const ConvCall& c) {
+  const int N = c.N, H = c.H, W = c.W, Kdim = c.Kdim, Ndim = c.Ndim;
+  const bool plain_taps = c.isc == 1 && c.osc == 1 && c.G == 1 && c.ntap_out == 1;
   // From the r01 sweep (scratch/bench_conv.py, B=32, U-Net shapes): 8-row tiles win everywhere; 32 output channels
   // per workgroup (grid.z walks the rest) beat 64, and 16 win when the grid would otherwise be < ~4 WGs per CU.
   if constexpr (KS == 3) {
     // small-Cin / large-image layers: persistent kernel with resident weights (see conv_mfma_fwd_p); it declines
     // (-1) shapes it does not cover, which fall through to the per-tile kernel below.
-    if (isc == 1 && osc == 1 && G == 1 && ntap_out == 1 && fwd_any_eligible(N, H, W, Kdim, Ndim, f16)) {
-      if (select_fwd_p(x, w, y, N, H, W, Kdim, Ndim, transposed, st, stats, tiles_out, nullptr, y2, split, x2, nullptr, f16,
-                       gsc, nullptr, wu) == 0)
-        return 0;
+    if (plain_taps && fwd_any_eligible(N, H, W, Kdim, Ndim, c.f16_operands)) {
+      if (select_fwd_p(c) == 0) return 0;
     }
-    if (isc == 1 && osc == 1 && G == 1 && ntap_out == 1 && (transposed & 1) && !stats && !tiles_out && !x2 && !y2 && !f16 &&
+    if (plain_taps && c.transposed_w && !c.stats && !c.tiles_out && !c.x2 && !c.y2 && !c.f16_operands &&
         fwd_p_n8_eligible(N, H, W, Kdim, Ndim)) {
-      if (select_fwd_p(x, w, y, N, H, W, Kdim, Ndim, transposed, st, nullptr, nullptr, nullptr) == 0) return 0;
+      if (select_fwd_p(c) == 0) return 0;
     }
   }
   const int nt = (Ndim + 15) / 16;
   const int tx = (W + TW - 1) / TW;
-  const int64_t wg16 = (int64_t)tx * ((H + 15) / 16) * N * ((nt + 1) / 2) * ntap_out;
-  const int64_t wg8 = (int64_t)tx * ((H + 7) / 8) * N * ((nt + 1) / 2) * ntap_out;
+  const int64_t wg16 = (int64_t)tx * ((H + 15) / 16) * N * ((nt + 1) / 2) * c.ntap_out;
+  const int64_t wg8 = (int64_t)tx * ((H + 7) / 8) * N * ((nt + 1) / 2) * c.ntap_out;
   // planes of <= 4 rows (discriminator 4x4 level): the 4-row tile halves the rows of padding every MFMA multiplies --
   // scratch/bench_conv_small.py, 256->256: 19.4 vs 29.1 us forward, 25.1 vs 32.7 us data-gradient at B=16 (28.7 vs 48.2 at 32)
   // 8x8 planes of the discriminator's deep levels: M-tiles of real pixels only -- four (2 rows x 8 columns) tiles per plane, 16
   // output channels per workgroup so that B=16 still gives one workgroup per CU.
   // (4x4 planes stay on the 4-row tile: a plane is ONE M-tile, and 64-channel workgroups leave 64 of them for 256 CUs --
   //  measured 71 us vs 19-25 us; there the limit is parallelism, not padded MFMAs.)
-  if (isc == 1 && osc == 1 && G == 1 && ntap_out == 1 && !f16 && H <= 8 && W <= 8 && H > 4)
-    return launch_fwd<KS, 8, 4, 1, 1, 8>(ARGS);
-  if (H <= 4 && isc == 1 && osc == 1) return launch_fwd<KS, 4, 4, 1, 1>(ARGS);
-  if (nt == 1) return launch_fwd<KS, 8, 4, 1, 1>(ARGS);
-  if (wg16 >= 512) return launch_fwd<KS, 16, 4, 1, 2>(ARGS);       // >= 2 workgroups per CU with the big tile
+  if (plain_taps && !c.f16_operands && H <= 8 && W <= 8 && H > 4) return launch_fwd<KS, 8, 4, 1, 1, 8>(c);
+  if (H <= 4 && c.isc == 1 && c.osc == 1) return launch_fwd<KS, 4, 4, 1, 1>(c);
+  if (nt == 1) return launch_fwd<KS, 8, 4, 1, 1>(c);
+  if (wg16 >= 512) return launch_fwd<KS, 16, 4, 1, 2>(c);       // >= 2 workgroups per CU with the big tile
   // mid-size grids: 32 output channels per workgroup for the forward form; the data-gradient form (float4 weight rows)
   // runs 10-17 % faster with 16 (same sweep: 51.3 vs 60.0 us at 16x16 256->256, 49.4 vs 59.3 us at B32 8x8)
-  if (wg8 >= 256 && !(transposed & 1)) return launch_fwd<KS, 8, 4, 1, 2>(ARGS);
-  return launch_fwd<KS, 8, 4, 1, 1>(ARGS);
-#undef ARGS
+  if (wg8 >= 256 && !c.transposed_w) return launch_fwd<KS, 8, 4, 1, 2>(c);
+  return launch_fwd<KS, 8, 4, 1, 1>(c);
 }
 
 // tuning hook: force a tile configuration (scratch/bench_conv.py sweeps these to fill dispatch_fwd's table)
 template <int KS>
-int dispatch_fwd_cfg(int cfg, const float* x, const float* w, float* y, int N, int H, int W, int Kdim, int Ndim,
-                     int transposed, hipStream_t st) {
-#define ARGS x, w, y, N, H, W, Kdim, Ndim, transposed, 1, 1, 1, 1, st
+int dispatch_fwd_cfg(int cfg, const ConvCall& c) {
   switch (cfg) {
-    case 0: return launch_fwd<KS, 16, 4, 1, 1>(ARGS);
-    case 1: return launch_fwd<KS, 8, 4, 1, 1>(ARGS);
-    case 2: return launch_fwd<KS, 4, 4, 1, 1>(ARGS);
-    case 3: return launch_fwd<KS, 16, 4, 1, 2>(ARGS);
-    case 4: return launch_fwd<KS, 8, 4, 1, 2>(ARGS);
-    case 5: return launch_fwd<KS, 4, 4, 1, 2>(ARGS);
-    case 6: return launch_fwd<KS, 8, 2, 2, 4>(ARGS);
-    case 7: return launch_fwd<KS, 4, 1, 4, 4>(ARGS);
-    case 8: return launch_fwd<KS, 8, 4, 1, 4>(ARGS);
-    case 9: return launch_fwd<KS, 4, 2, 2, 4>(ARGS);
-    case 10: return launch_fwd<KS, 8, 2, 2, 2>(ARGS);
-    case 11: return launch_fwd<KS, 16, 2, 2, 2>(ARGS);
+    case 0: return launch_fwd<KS, 16, 4, 1, 1>(c);
+    case 1: return launch_fwd<KS, 8, 4, 1, 1>(c);
+    case 2: return launch_fwd<KS, 4, 4, 1, 1>(c);
+    case 3: return launch_fwd<KS, 16, 4, 1, 2>(c);
+    case 4: return launch_fwd<KS, 8, 4, 1, 2>(c);
+    case 5: return launch_fwd<KS, 4, 4, 1, 2>(c);
+    case 6: return launch_fwd<KS, 8, 2, 2, 4>(c);
+    case 7: return launch_fwd<KS, 4, 1, 4, 4>(c);
+    case 8: return launch_fwd<KS, 8, 4, 1, 4>(c);
+    case 9: return launch_fwd<KS, 4, 2, 2, 4>(c);
+    case 10: return launch_fwd<KS, 8, 2, 2, 2>(c);
+    case 11: return launch_fwd<KS, 16, 2, 2, 2>(c);
     default: break;
   }
-#undef ARGS
   if (KS == 3) {
-#define PARGS x, w, y, N, H, W, Kdim, Ndim, transposed, st
     switch (cfg) {
-      case 20: return launch_fwd_p<3, 8, 1, 1>(PARGS);
-      case 21: return launch_fwd_p<3, 8, 1, 2>(PARGS);
-      case 22: return launch_fwd_p<3, 16, 1, 1>(PARGS);
-      case 23: return launch_fwd_p<3, 16, 1, 2>(PARGS);
-      case 24: return launch_fwd_p<3, 8, 2, 1>(PARGS);
-      case 25: return launch_fwd_p<3, 8, 2, 2>(PARGS);
-      case 26: return launch_fwd_p<3, 16, 2, 1>(PARGS);
-      case 27: return launch_fwd_p<3, 16, 2, 2>(PARGS);
-      case 28: return launch_fwd_p<3, 8, 1, 4>(PARGS);
-      case 29: return launch_fwd_p<3, 16, 1, 4>(PARGS);
-      case 30: return launch_fwd_p<3, 16, 1, 1, false, false, true>(PARGS);      // Winograd F(2x2,3x3) forms
-      case 31: return launch_fwd_p<3, 16, 1, 2, false, false, true>(PARGS);
-      case 32: return launch_fwd_p<3, 16, 1, 4, false, false, true>(PARGS);
+      case 20: return launch_fwd_p<3, 8, 1, 1>(c);
+      case 21: return launch_fwd_p<3, 8, 1, 2>(c);
+      case 22: return launch_fwd_p<3, 16, 1, 1>(c);
+      case 23: return launch_fwd_p<3, 16, 1, 2>(c);
+      case 24: return launch_fwd_p<3, 8, 2, 1>(c);
+      case 25: return launch_fwd_p<3, 8, 2, 2>(c);
+      case 26: return launch_fwd_p<3, 16, 2, 1>(c);
+      case 27: return launch_fwd_p<3, 16, 2, 2>(c);
+      case 28: return launch_fwd_p<3, 8, 1, 4>(c);
+      case 29: return launch_fwd_p<3, 16, 1, 4>(c);
+      case 30: return launch_fwd_p<3, 16, 1, 1, false, false, true>(c);      // Winograd F(2x2,3x3) forms
+      case 31: return launch_fwd_p<3, 16, 1, 2, false, false, true>(c);
+      case 32: return launch_fwd_p<3, 16, 1, 4, false, false, true>(c);
       default: break;
     }
-#undef PARGS
   }
   return -1;
 }
@@ -2725,6 +2646,28 @@ int launch_wgrad(const float* x, const float* gy, float* part, int N, int H, int
   return 0;
 }
 
+// ---- what every conv entry point below shares ------------------------------------------------------------------------------------
+// the operands, shape and stream of a call; the entry point then sets its few other fields by name
+inline ConvCall conv_call(const void* x, const float* w, void* y, int N, int H, int W, int Kdim, int Ndim, void* stream) {
+  ConvCall c;
+  c.x = x; c.w = w; c.y = y;
+  c.N = N; c.H = H; c.W = W; c.Kdim = Kdim; c.Ndim = Ndim;
+  c.stream = (hipStream_t)stream;
+  return c;
+}
+// the C ABI's `transposed` bit set, decoded once: bit 0 = transposed weights (data-gradient), bit 1 = accumulate into y
+inline void set_transposed(ConvCall& c, int transposed) {
+  c.transposed_w = (transposed & 1) != 0;
+  c.accumulate = (transposed & 2) != 0;
+}
+inline int finish(int rc) {                   // rc of a launcher: -1 = the form is not covered, nothing launched
+  SMSUT_REQUIRE(rc == 0);
+  SMSUT_LAUNCH_CHECK();
+  return SMSUT_OK;
+}
+inline int run_p(const ConvCall& c) { return finish(select_fwd_p(c)); }       // persistent / Winograd kernels only
+inline int run(const ConvCall& c, int KS = 3) { return finish(KS == 1 ? dispatch_fwd<1>(c) : dispatch_fwd<3>(c)); }
+
 }  // namespace
 
 extern "C" {
@@ -2760,11 +2703,10 @@ int smsut_conv2d_fwd_mfma_pre(const float* x, const float* w, float* y, int N, i
   SMSUT_REQUIRE(x && w && y && N > 0 && H > 0 && W > 0);
   SMSUT_REQUIRE(smsut_conv2d_mfma_supported(KS, 1, (KS - 1) / 2, Kdim, Ndim));
   SMSUT_REQUIRE(!transposed || (Kdim % 4) == 0);
-  hipStream_t st = (hipStream_t)stream;
-  if (KS == 1) dispatch_fwd<1>(x, w, y, N, H, W, Kdim, Ndim, transposed, 1, 1, 1, 1, st);
-  else dispatch_fwd<3>(x, w, y, N, H, W, Kdim, Ndim, transposed, 1, 1, 1, 1, st, nullptr, nullptr, nullptr, nullptr, 0, false, nullptr, wu);
-  SMSUT_LAUNCH_CHECK();
-  return SMSUT_OK;
+  ConvCall c = conv_call(x, w, y, N, H, W, Kdim, Ndim, stream);
+  set_transposed(c, transposed);
+  c.wu = wu;
+  return run(c, KS);
 }
 int smsut_conv2d_fwd_mfma(const float* x, const float* w, float* y, int N, int H, int W, int Kdim, int Ndim, int KS,
                           int transposed, void* stream) {
@@ -2780,11 +2722,9 @@ int smsut_conv2d_fwd_mfma_stats_inaff_pre(const float* x, const float* w, float*
   SMSUT_REQUIRE(x && w && y && stats && mean && rstd && gamma && beta && N > 0 && H > 0 && W > 0);
   SMSUT_REQUIRE(fwd_any_eligible(N, H, W, Kdim, Ndim, false));
   const AffRef a{mean, rstd, gamma, beta, slope};
-  const int rc = select_fwd_p(x, w, y, N, H, W, Kdim, Ndim, 0, (hipStream_t)stream, stats, nullptr, nullptr, nullptr, 0, nullptr, &a,
-                              false, nullptr, nullptr, wu);
-  SMSUT_REQUIRE(rc == 0);
-  SMSUT_LAUNCH_CHECK();
-  return SMSUT_OK;
+  ConvCall c = conv_call(x, w, y, N, H, W, Kdim, Ndim, stream);
+  c.stats = stats; c.aff = &a; c.wu = wu;
+  return run_p(c);
 }
 int smsut_conv2d_fwd_mfma_stats_inaff(const float* x, const float* w, float* y, float* stats, const float* mean,
                                       const float* rstd, const float* gamma, const float* beta, float slope, int N, int H,
@@ -2809,11 +2749,9 @@ int smsut_conv2d_fwd_mfma_stats_sc_pre(const float* x, const float* xb, const fl
                                        void* stream) {
   SMSUT_REQUIRE(x && w && wsc && y && ysc && stats && stats_sc && smsut_conv2d_fwd_sc_supported(N, H, W, Kdim, Ndim, xb != nullptr));
   const ScRef sc{wsc, ysc, stats_sc};
-  const int rc = select_fwd_p(x, w, y, N, H, W, Kdim, Ndim, 0, (hipStream_t)stream, stats, nullptr, nullptr, nullptr, 0, xb, nullptr,
-                              false, nullptr, &sc, wu);
-  SMSUT_REQUIRE(rc == 0);
-  SMSUT_LAUNCH_CHECK();
-  return SMSUT_OK;
+  ConvCall c = conv_call(x, w, y, N, H, W, Kdim, Ndim, stream);
+  c.x2 = xb; c.stats = stats; c.sc = &sc; c.wu = wu;
+  return run_p(c);
 }
 int smsut_conv2d_fwd_mfma_stats_sc(const float* x, const float* xb, const float* w, const float* wsc, float* y, float* ysc,
                                    float* stats, float* stats_sc, int N, int H, int W, int Kdim, int Ndim, void* stream) {
@@ -2830,11 +2768,9 @@ int smsut_conv2d_fwd_mfma_stats_sc_f16(const float* x, const float* xb, const fl
                                        float* stats, float* stats_sc, int N, int H, int W, int Kdim, int Ndim, void* stream) {
   SMSUT_REQUIRE(x && w && wsc && y && ysc && stats && stats_sc && smsut_conv2d_fwd_sc_f16_supported(N, H, W, Kdim, Ndim, xb != nullptr));
   const ScRef sc{wsc, ysc, stats_sc};
-  const int rc = select_fwd_p(x, w, y, N, H, W, Kdim, Ndim, 0, (hipStream_t)stream, stats, nullptr, nullptr, nullptr, 0, xb, nullptr,
-                              true, nullptr, &sc);
-  SMSUT_REQUIRE(rc == 0);
-  SMSUT_LAUNCH_CHECK();
-  return SMSUT_OK;
+  ConvCall c = conv_call(x, w, y, N, H, W, Kdim, Ndim, stream);
+  c.x2 = xb; c.stats = stats; c.sc = &sc; c.f16_operands = true;
+  return run_p(c);
 }
 
 // Data-gradient of that pair: gx = dgrad3x3(gy, w) + dgrad1x1(gs, wsc) in one pass (gy, gs [N,H,W,Cout]; w, wsc the forward
@@ -2852,11 +2788,9 @@ int smsut_conv2d_dgrad_mfma_sc(const float* gy, const float* gs, const float* w,
                                int split, int N, int H, int W, int Cout, int Cin, void* stream) {
   SMSUT_REQUIRE(gy && gs && w && wsc && gxa && smsut_conv2d_dgrad_sc_supported(N, H, W, Cout, Cin, gxb ? split : 0));
   const ScRef sc{wsc, nullptr, nullptr};
-  const int rc = select_fwd_p(gy, w, gxa, N, H, W, 2 * Cout, Cin, 1, (hipStream_t)stream, nullptr, nullptr, nullptr, gxb, gxb ? split : 0,
-                              gs, nullptr, false, nullptr, &sc);
-  SMSUT_REQUIRE(rc == 0);
-  SMSUT_LAUNCH_CHECK();
-  return SMSUT_OK;
+  ConvCall c = conv_call(gy, w, gxa, N, H, W, 2 * Cout, Cin, stream);
+  c.x2 = gs; c.y2 = gxb; c.split = gxb ? split : 0; c.sc = &sc; c.transposed_w = true;
+  return run_p(c);
 }
 
 // fp16 RESULT STORAGE (config 5, r04): the same passes, the raw conv outputs y (and ysc) stored as fp16 [N,H,W,Ndim] -- block-internal
@@ -2872,22 +2806,18 @@ int smsut_conv2d_f16_hs_supported(int N, int H, int W, int Kdim, int Ndim, int c
 int smsut_conv2d_fwd_mfma_stats_f16_hs(const float* x, const float* xb, const float* w, void* y16, float* stats, int N, int H, int W,
                                        int Kdim, int Ndim, void* stream) {
   SMSUT_REQUIRE(x && w && y16 && stats && Kdim != 8 && smsut_conv2d_f16_hs_supported(N, H, W, Kdim, Ndim, xb != nullptr));
-  const int rc = select_fwd_p(x, w, (float*)y16, N, H, W, Kdim, Ndim, 0, (hipStream_t)stream, stats, nullptr, nullptr, nullptr, 0, xb,
-                              nullptr, true, nullptr, nullptr, nullptr, 1);
-  SMSUT_REQUIRE(rc == 0);
-  SMSUT_LAUNCH_CHECK();
-  return SMSUT_OK;
+  ConvCall c = conv_call(x, w, y16, N, H, W, Kdim, Ndim, stream);
+  c.x2 = xb; c.stats = stats; c.f16_operands = true; c.out_f16 = true;
+  return run_p(c);
 }
 // ... whose INPUT is fp16 as well (conv2 of the block reading the activated a1 that smsut_instnorm_fwd_partials_hs2 stored as fp16):
 // the operands are the bits the fp32-input form rounds a1 to -- same result, 2 bytes per element less to read
 int smsut_conv2d_fwd_mfma_stats_f16_hsx(const void* x16, const float* w, void* y16, float* stats, int N, int H, int W, int Kdim,
                                         int Ndim, void* stream) {
   SMSUT_REQUIRE(x16 && w && y16 && stats && smsut_conv2d_f16_hs_supported(N, H, W, Kdim, Ndim, 0));
-  const int rc = select_fwd_p((const float*)x16, w, (float*)y16, N, H, W, Kdim, Ndim, 0, (hipStream_t)stream, stats, nullptr, nullptr,
-                              nullptr, 0, nullptr, nullptr, true, nullptr, nullptr, nullptr, 3);
-  SMSUT_REQUIRE(rc == 0);
-  SMSUT_LAUNCH_CHECK();
-  return SMSUT_OK;
+  ConvCall c = conv_call(x16, w, y16, N, H, W, Kdim, Ndim, stream);
+  c.stats = stats; c.f16_operands = true; c.in_f16 = true; c.out_f16 = true;
+  return run_p(c);
 }
 // ... reading the RAW fp16 conv1 output y1 and applying lrelu(IN(.)) while staging (mean / rstd [N,Kdim], gamma / beta [Kdim]): the
 // half-storage twin of smsut_conv2d_fwd_mfma_stats_inaff -- the activated a1 is never built
@@ -2896,22 +2826,18 @@ int smsut_conv2d_fwd_mfma_stats_inaff_f16_hsx(const void* y1_16, const float* w,
                                               int W, int Kdim, int Ndim, void* stream) {
   SMSUT_REQUIRE(y1_16 && w && y16 && stats && mean && rstd && gamma && beta && Kdim != 8 && smsut_conv2d_f16_hs_supported(N, H, W, Kdim, Ndim, 0));
   const AffRef a{mean, rstd, gamma, beta, slope};
-  const int rc = select_fwd_p((const float*)y1_16, w, (float*)y16, N, H, W, Kdim, Ndim, 0, (hipStream_t)stream, stats, nullptr, nullptr,
-                              nullptr, 0, nullptr, &a, true, nullptr, nullptr, nullptr, 3);
-  SMSUT_REQUIRE(rc == 0);
-  SMSUT_LAUNCH_CHECK();
-  return SMSUT_OK;
+  ConvCall c = conv_call(y1_16, w, y16, N, H, W, Kdim, Ndim, stream);
+  c.stats = stats; c.aff = &a; c.f16_operands = true; c.in_f16 = true; c.out_f16 = true;
+  return run_p(c);
 }
 int smsut_conv2d_fwd_mfma_stats_sc_f16_hs(const float* x, const float* xb, const float* w, const float* wsc, void* y16, void* ysc16,
                                           float* stats, float* stats_sc, int N, int H, int W, int Kdim, int Ndim, void* stream) {
   SMSUT_REQUIRE(x && w && wsc && y16 && ysc16 && stats && stats_sc && smsut_conv2d_f16_hs_supported(N, H, W, Kdim, Ndim, xb != nullptr) &&
                 (Kdim == 8 || smsut_conv2d_fwd_sc_f16_supported(N, H, W, Kdim, Ndim, xb != nullptr)));
-  const ScRef sc{wsc, (float*)ysc16, stats_sc};
-  const int rc = select_fwd_p(x, w, (float*)y16, N, H, W, Kdim, Ndim, 0, (hipStream_t)stream, stats, nullptr, nullptr, nullptr, 0, xb,
-                              nullptr, Kdim != 8, nullptr, &sc, nullptr, 1);
-  SMSUT_REQUIRE(rc == 0);
-  SMSUT_LAUNCH_CHECK();
-  return SMSUT_OK;
+  const ScRef sc{wsc, (float*)ysc16, stats_sc};      // (the kernel argument's type; fp16 storage under out_f16)
+  ConvCall c = conv_call(x, w, y16, N, H, W, Kdim, Ndim, stream);
+  c.x2 = xb; c.stats = stats; c.sc = &sc; c.f16_operands = Kdim != 8; c.out_f16 = true;
+  return run_p(c);
 }
 
 // conv2's data-gradient with the IN1 / LeakyReLU mask and backward statistics (smsut_conv2d_dgrad_mfma_bwdstats_f16) reading an fp16 y1
@@ -2919,12 +2845,10 @@ int smsut_conv2d_dgrad_mfma_bwdstats_f16_hs(const float* gy, const float* w, flo
                                             const float* mean, const float* rstd, const float* gamma, const float* beta,
                                             const float* gsc, float slope, int N, int H, int W, int Kdim, int Ndim, void* stream) {
   SMSUT_REQUIRE(gy && w && gz && stats && y1_16 && mean && rstd && gamma && beta && smsut_conv2d_f16_hs_supported(N, H, W, Kdim, Ndim, 0));
-  const BstRef b{(const float*)y1_16, mean, rstd, gamma, beta, slope};
-  const int rc = select_fwd_p(gy, w, gz, N, H, W, Kdim, Ndim, 1, (hipStream_t)stream, stats, nullptr, &b, nullptr, 0, nullptr,
-                              nullptr, true, gsc, nullptr, nullptr, 1);
-  SMSUT_REQUIRE(rc == 0);
-  SMSUT_LAUNCH_CHECK();
-  return SMSUT_OK;
+  const BstRef b{(const float*)y1_16, mean, rstd, gamma, beta, slope};      // (the kernel argument's type; fp16 storage under out_f16)
+  ConvCall c = conv_call(gy, w, gz, N, H, W, Kdim, Ndim, stream);
+  c.stats = stats; c.bst = &b; c.gsc = gsc; c.transposed_w = true; c.f16_operands = true; c.out_f16 = true;
+  return run_p(c);
 }
 
 // ... with fp16 operands (config 5): gsc = {s, 1/s} of smsut_absmax_scale2(gy, gs) -- the two gradients share the accumulators, so
@@ -2938,11 +2862,9 @@ int smsut_conv2d_dgrad_mfma_sc_f16(const float* gy, const float* gs, const float
                                    const float* gsc, int split, int N, int H, int W, int Cout, int Cin, void* stream) {
   SMSUT_REQUIRE(gy && gs && w && wsc && gxa && gsc && smsut_conv2d_dgrad_sc_f16_supported(N, H, W, Cout, Cin, gxb ? split : 0));
   const ScRef sc{wsc, nullptr, nullptr};
-  const int rc = select_fwd_p(gy, w, gxa, N, H, W, 2 * Cout, Cin, 1, (hipStream_t)stream, nullptr, nullptr, nullptr, gxb, gxb ? split : 0,
-                              gs, nullptr, true, gsc, &sc);
-  SMSUT_REQUIRE(rc == 0);
-  SMSUT_LAUNCH_CHECK();
-  return SMSUT_OK;
+  ConvCall c = conv_call(gy, w, gxa, N, H, W, 2 * Cout, Cin, stream);
+  c.x2 = gs; c.y2 = gxb; c.split = gxb ? split : 0; c.sc = &sc; c.gsc = gsc; c.transposed_w = true; c.f16_operands = true;
+  return run_p(c);
 }
 
 // Which arithmetic a 3x3 stride-1 fp32 conv call (forward or data-gradient, any fused form) runs for this shape: 0 = direct
@@ -2970,11 +2892,9 @@ int smsut_conv2d_mfma_cat_supported(int N, int H, int W, int Kdim, int Ndim) {
 int smsut_conv2d_fwd_mfma_stats_cat_pre(const float* xa, const float* xb, const float* w, float* y, float* stats, int N, int H,
                                         int W, int Kdim, int Ndim, const float* wu, void* stream) {
   SMSUT_REQUIRE(xa && xb && w && y && stats && smsut_conv2d_mfma_cat_supported(N, H, W, Kdim, Ndim));
-  const int rc = dispatch_fwd<3>(xa, w, y, N, H, W, Kdim, Ndim, 0, 1, 1, 1, 1, (hipStream_t)stream, stats, nullptr, xb, nullptr, 0, false,
-                                 nullptr, wu);
-  SMSUT_REQUIRE(rc == 0);
-  SMSUT_LAUNCH_CHECK();
-  return SMSUT_OK;
+  ConvCall c = conv_call(xa, w, y, N, H, W, Kdim, Ndim, stream);
+  c.x2 = xb; c.stats = stats; c.wu = wu;
+  return run(c);
 }
 int smsut_conv2d_fwd_mfma_stats_cat(const float* xa, const float* xb, const float* w, float* y, float* stats, int N, int H,
                                     int W, int Kdim, int Ndim, void* stream) {
@@ -2996,11 +2916,10 @@ int smsut_conv2d_fwd_mfma_split_pre(const float* x, const float* w, float* ya, f
                                     int Kdim, int Ndim, int transposed, const float* wu, void* stream) {
   SMSUT_REQUIRE(x && w && ya && yb && N > 0 && H > 0 && W > 0 && (transposed & ~3) == 0);
   SMSUT_REQUIRE(smsut_conv2d_mfma_split_supported(N, H, W, Kdim, Ndim, split));
-  const int rc = dispatch_fwd<3>(x, w, ya, N, H, W, Kdim, Ndim, transposed, 1, 1, 1, 1, (hipStream_t)stream, nullptr, nullptr,
-                                 nullptr, yb, split, false, nullptr, wu);
-  SMSUT_REQUIRE(rc == 0);
-  SMSUT_LAUNCH_CHECK();
-  return SMSUT_OK;
+  ConvCall c = conv_call(x, w, ya, N, H, W, Kdim, Ndim, stream);
+  set_transposed(c, transposed);
+  c.y2 = yb; c.split = split; c.wu = wu;
+  return run(c);
 }
 int smsut_conv2d_fwd_mfma_split(const float* x, const float* w, float* ya, float* yb, int split, int N, int H, int W,
                                 int Kdim, int Ndim, int transposed, void* stream) {
@@ -3016,17 +2935,17 @@ int smsut_convT2x2_mfma_supported(int Cin, int Cout) { return Cin >= 4 && (Cin %
 int smsut_convT2x2_fwd_mfma(const float* x, const float* w, float* y, int N, int H, int W, int Cin, int Cout,
                             void* stream) {
   SMSUT_REQUIRE(x && w && y && N > 0 && H > 0 && W > 0 && smsut_convT2x2_mfma_supported(Cin, Cout));
-  dispatch_fwd<1>(x, w, y, N, H, W, Cin, Cout, 0, 1, 2, 1, 4, (hipStream_t)stream);
-  SMSUT_LAUNCH_CHECK();
-  return SMSUT_OK;
+  ConvCall c = conv_call(x, w, y, N, H, W, Cin, Cout, stream);
+  c.osc = 2; c.ntap_out = 4;
+  return run(c, 1);
 }
 
 int smsut_convT2x2_dgrad_mfma(const float* gy, const float* w, float* gx, int N, int H, int W, int Cin, int Cout,
                               void* stream) {
   SMSUT_REQUIRE(gy && w && gx && N > 0 && H > 0 && W > 0 && smsut_convT2x2_mfma_supported(Cin, Cout));
-  dispatch_fwd<1>(gy, w, gx, N, H, W, Cout, Cin, 1, 2, 1, 4, 1, (hipStream_t)stream);
-  SMSUT_LAUNCH_CHECK();
-  return SMSUT_OK;
+  ConvCall c = conv_call(gy, w, gx, N, H, W, Cout, Cin, stream);
+  c.transposed_w = true; c.isc = 2; c.G = 4;
+  return run(c, 1);
 }
 
 // Forward conv that also emits the InstanceNorm statistics partials of its output (see conv_mfma_fwd).
@@ -3036,9 +2955,11 @@ int smsut_conv2d_mfma_tiles(int N, int H, int W, int Kdim, int Ndim, int KS, int
   // f16: the tiles of the fp16-operand entry points (r03: the fp32 forms of a shape may run a Winograd kernel on 16-row items
   // where the fp16 ones keep the direct kernel's)
   int tiles = 0;
-  if (KS == 1) dispatch_fwd<1>(nullptr, nullptr, nullptr, N, H, W, Kdim, Ndim, 0, 1, 1, 1, 1, nullptr, nullptr, &tiles);
-  else dispatch_fwd<3>(nullptr, nullptr, nullptr, N, H, W, Kdim, Ndim, 0, 1, 1, 1, 1, nullptr, nullptr, &tiles, nullptr, nullptr, 0,
-                       f16 != 0);
+  ConvCall c = conv_call(nullptr, nullptr, nullptr, N, H, W, Kdim, Ndim, nullptr);
+  c.tiles_out = &tiles;
+  c.f16_operands = KS != 1 && f16 != 0;
+  if (KS == 1) dispatch_fwd<1>(c);
+  else dispatch_fwd<3>(c);
   return tiles;
 }
 
@@ -3051,11 +2972,10 @@ int smsut_conv2d_fwd_mfma_stats_pre(const float* x, const float* w, float* y, fl
                                     int Ndim, int KS, const float* wu, void* stream) {
   SMSUT_REQUIRE(x && w && y && stats && N > 0 && H > 0 && W > 0);
   SMSUT_REQUIRE(smsut_conv2d_mfma_supported(KS, 1, (KS - 1) / 2, Kdim, Ndim));
-  hipStream_t st = (hipStream_t)stream;
-  if (KS == 1) dispatch_fwd<1>(x, w, y, N, H, W, Kdim, Ndim, 0, 1, 1, 1, 1, st, stats);
-  else dispatch_fwd<3>(x, w, y, N, H, W, Kdim, Ndim, 0, 1, 1, 1, 1, st, stats, nullptr, nullptr, nullptr, 0, false, nullptr, wu);
-  SMSUT_LAUNCH_CHECK();
-  return SMSUT_OK;
+  ConvCall c = conv_call(x, w, y, N, H, W, Kdim, Ndim, stream);
+  c.stats = stats;
+  c.wu = wu;
+  return run(c, KS);
 }
 int smsut_conv2d_fwd_mfma_stats(const float* x, const float* w, float* y, float* stats, int N, int H, int W, int Kdim,
                                 int Ndim, int KS, void* stream) {
@@ -3071,12 +2991,9 @@ int smsut_conv2d_dgrad_mfma_bwdstats_pre(const float* gy, const float* w, float*
   SMSUT_REQUIRE(gy && w && gz && stats && y1 && mean && rstd && gamma && beta && N > 0 && H > 0 && W > 0);
   SMSUT_REQUIRE(fwd_any_eligible(N, H, W, Kdim, Ndim, false));
   const BstRef b{y1, mean, rstd, gamma, beta, slope};
-  hipStream_t st = (hipStream_t)stream;
-  const int rc = select_fwd_p(gy, w, gz, N, H, W, Kdim, Ndim, 1, st, stats, nullptr, &b, nullptr, 0, nullptr, nullptr, false, nullptr,
-                              nullptr, wu);
-  SMSUT_REQUIRE(rc == 0);
-  SMSUT_LAUNCH_CHECK();
-  return SMSUT_OK;
+  ConvCall c = conv_call(gy, w, gz, N, H, W, Kdim, Ndim, stream);
+  c.stats = stats; c.bst = &b; c.transposed_w = true; c.wu = wu;
+  return run_p(c);
 }
 int smsut_conv2d_dgrad_mfma_bwdstats(const float* gy, const float* w, float* gz, float* stats, const float* y1,
                                      const float* mean, const float* rstd, const float* gamma, const float* beta,
@@ -3086,7 +3003,7 @@ int smsut_conv2d_dgrad_mfma_bwdstats(const float* gy, const float* w, float* gz,
 
 // ---- `_fin` forms (r05): the same launches with the InstanceNorm statistics FINALISED INSIDE THE LAUNCH (common.h, FinRef): the
 // workgroup whose partials complete an image combines them (in_moments_final's order: same bits) -- the separate
-// smsut_in_finalize_* launch behind every statistics-producing conv of a fused BasicBlock (/root/reference/network/blocks.py:70-79:
+// smsut_in_finalize_* launch behind every statistics-producing conv of a fused BasicBlock (network/blocks.py:70-79 of the original model:
 // conv -> InstanceNorm, three times per block forward, once more per block backward) disappears.  tickets: int [N], ZERO on entry,
 // zero again when the launch is over (the caller hands out slices of one zero-initialised pool).  wu (nullable): the caller's
 // prepared Winograd image for this call (the `_pre` argument).  fp32 operands.
@@ -3098,11 +3015,9 @@ int smsut_conv2d_fwd_mfma_stats_sc_fin(const float* x, const float* xb, const fl
   SMSUT_REQUIRE(smsut_conv2d_fwd_sc_supported(N, H, W, Kdim, Ndim, xb != nullptr));
   const ScRef sc{wsc, ysc, stats_sc};
   const FinRef fin{tickets, mean, rstd, mean_sc, rstd_sc, eps};
-  const int rc = select_fwd_p(x, w, y, N, H, W, Kdim, Ndim, 0, (hipStream_t)stream, stats, nullptr, nullptr, nullptr, 0, xb, nullptr,
-                              false, nullptr, &sc, wu, 0, &fin);
-  SMSUT_REQUIRE(rc == 0);
-  SMSUT_LAUNCH_CHECK();
-  return SMSUT_OK;
+  ConvCall c = conv_call(x, w, y, N, H, W, Kdim, Ndim, stream);
+  c.x2 = xb; c.stats = stats; c.sc = &sc; c.fin = &fin; c.wu = wu;
+  return run_p(c);
 }
 int smsut_conv2d_fwd_mfma_stats_inaff_fin(const float* x, const float* w, float* y, float* stats, const float* mean,
                                           const float* rstd, const float* gamma, const float* beta, float slope, int* tickets,
@@ -3112,11 +3027,9 @@ int smsut_conv2d_fwd_mfma_stats_inaff_fin(const float* x, const float* w, float*
   SMSUT_REQUIRE(fwd_any_eligible(N, H, W, Kdim, Ndim, false));
   const AffRef a{mean, rstd, gamma, beta, slope};
   const FinRef fin{tickets, mean_out, rstd_out, nullptr, nullptr, eps};
-  const int rc = select_fwd_p(x, w, y, N, H, W, Kdim, Ndim, 0, (hipStream_t)stream, stats, nullptr, nullptr, nullptr, 0, nullptr, &a,
-                              false, nullptr, nullptr, wu, 0, &fin);
-  SMSUT_REQUIRE(rc == 0);
-  SMSUT_LAUNCH_CHECK();
-  return SMSUT_OK;
+  ConvCall c = conv_call(x, w, y, N, H, W, Kdim, Ndim, stream);
+  c.stats = stats; c.aff = &a; c.fin = &fin; c.wu = wu;
+  return run_p(c);
 }
 // ... the data-gradient with backward statistics: a_mean / b_mean [N][Ndim] = mean(gz), mean(gz * xhat) (what smsut_in_finalize_bwd writes)
 int smsut_conv2d_dgrad_mfma_bwdstats_fin(const float* gy, const float* w, float* gz, float* stats, const float* y1,
@@ -3127,21 +3040,17 @@ int smsut_conv2d_dgrad_mfma_bwdstats_fin(const float* gy, const float* w, float*
   SMSUT_REQUIRE(fwd_any_eligible(N, H, W, Kdim, Ndim, false));
   const BstRef b{y1, mean, rstd, gamma, beta, slope};
   const FinRef fin{tickets, a_mean, b_mean, nullptr, nullptr, 0.f};
-  const int rc = select_fwd_p(gy, w, gz, N, H, W, Kdim, Ndim, 1, (hipStream_t)stream, stats, nullptr, &b, nullptr, 0, nullptr, nullptr,
-                              false, nullptr, nullptr, wu, 0, &fin);
-  SMSUT_REQUIRE(rc == 0);
-  SMSUT_LAUNCH_CHECK();
-  return SMSUT_OK;
+  ConvCall c = conv_call(gy, w, gz, N, H, W, Kdim, Ndim, stream);
+  c.stats = stats; c.bst = &b; c.fin = &fin; c.transposed_w = true; c.wu = wu;
+  return run_p(c);
 }
 
 int smsut_conv2d_fwd_mfma_cfg(const float* x, const float* w, float* y, int N, int H, int W, int Kdim, int Ndim, int KS,
                               int transposed, int cfg, void* stream) {
   SMSUT_REQUIRE(x && w && y && N > 0 && H > 0 && W > 0 && smsut_conv2d_mfma_supported(KS, 1, (KS - 1) / 2, Kdim, Ndim));
-  const int rc = KS == 1 ? dispatch_fwd_cfg<1>(cfg, x, w, y, N, H, W, Kdim, Ndim, transposed, (hipStream_t)stream)
-                         : dispatch_fwd_cfg<3>(cfg, x, w, y, N, H, W, Kdim, Ndim, transposed, (hipStream_t)stream);
-  SMSUT_REQUIRE(rc == 0);
-  SMSUT_LAUNCH_CHECK();
-  return SMSUT_OK;
+  ConvCall c = conv_call(x, w, y, N, H, W, Kdim, Ndim, stream);
+  set_transposed(c, transposed);
+  return finish(KS == 1 ? dispatch_fwd_cfg<1>(cfg, c) : dispatch_fwd_cfg<3>(cfg, c));
 }
 
 int smsut_conv2d_wgrad_mfma_supported(int KS, int stride, int pad, int Cin, int Cout) {
@@ -3376,39 +3285,33 @@ int smsut_conv2d_f16_supported(int KS, int Kdim, int Ndim) {
 int smsut_conv2d_fwd_mfma_f16(const float* x, const float* w, float* y, const float* gsc, int N, int H, int W, int Kdim,
                               int Ndim, int KS, int transposed, void* stream) {
   SMSUT_REQUIRE(x && w && y && N > 0 && H > 0 && W > 0 && smsut_conv2d_f16_supported(KS, Kdim, Ndim));
-  hipStream_t st = (hipStream_t)stream;
-  if (KS == 1) dispatch_fwd<1>(x, w, y, N, H, W, Kdim, Ndim, transposed, 1, 1, 1, 1, st, nullptr, nullptr, nullptr, nullptr, 0, true, gsc);
-  else dispatch_fwd<3>(x, w, y, N, H, W, Kdim, Ndim, transposed, 1, 1, 1, 1, st, nullptr, nullptr, nullptr, nullptr, 0, true, gsc);
-  SMSUT_LAUNCH_CHECK();
-  return SMSUT_OK;
+  ConvCall c = conv_call(x, w, y, N, H, W, Kdim, Ndim, stream);
+  set_transposed(c, transposed);
+  c.gsc = gsc; c.f16_operands = true;
+  return run(c, KS);
 }
 int smsut_conv2d_fwd_mfma_stats_f16(const float* x, const float* w, float* y, float* stats, int N, int H, int W, int Kdim,
                                     int Ndim, int KS, void* stream) {
   SMSUT_REQUIRE(x && w && y && stats && N > 0 && H > 0 && W > 0 && smsut_conv2d_f16_supported(KS, Kdim, Ndim));
-  hipStream_t st = (hipStream_t)stream;
-  if (KS == 1) dispatch_fwd<1>(x, w, y, N, H, W, Kdim, Ndim, 0, 1, 1, 1, 1, st, stats, nullptr, nullptr, nullptr, 0, true, nullptr);
-  else dispatch_fwd<3>(x, w, y, N, H, W, Kdim, Ndim, 0, 1, 1, 1, 1, st, stats, nullptr, nullptr, nullptr, 0, true, nullptr);
-  SMSUT_LAUNCH_CHECK();
-  return SMSUT_OK;
+  ConvCall c = conv_call(x, w, y, N, H, W, Kdim, Ndim, stream);
+  c.stats = stats; c.f16_operands = true;
+  return run(c, KS);
 }
 int smsut_conv2d_fwd_mfma_stats_cat_f16(const float* xa, const float* xb, const float* w, float* y, float* stats, int N,
                                         int H, int W, int Kdim, int Ndim, void* stream) {
   SMSUT_REQUIRE(xa && xb && w && y && stats && smsut_conv2d_mfma_cat_supported(N, H, W, Kdim, Ndim));
-  const int rc = dispatch_fwd<3>(xa, w, y, N, H, W, Kdim, Ndim, 0, 1, 1, 1, 1, (hipStream_t)stream, stats, nullptr, xb, nullptr,
-                                 0, true, nullptr);
-  SMSUT_REQUIRE(rc == 0);
-  SMSUT_LAUNCH_CHECK();
-  return SMSUT_OK;
+  ConvCall c = conv_call(xa, w, y, N, H, W, Kdim, Ndim, stream);
+  c.x2 = xb; c.stats = stats; c.f16_operands = true;
+  return run(c);
 }
 int smsut_conv2d_fwd_mfma_split_f16(const float* x, const float* w, float* ya, float* yb, const float* gsc, int split, int N,
                                     int H, int W, int Kdim, int Ndim, int transposed, void* stream) {
   SMSUT_REQUIRE(x && w && ya && yb && N > 0 && H > 0 && W > 0 && (transposed & ~3) == 0 && Kdim % 16 == 0);
   SMSUT_REQUIRE(smsut_conv2d_mfma_split_supported(N, H, W, Kdim, Ndim, split));
-  const int rc = dispatch_fwd<3>(x, w, ya, N, H, W, Kdim, Ndim, transposed, 1, 1, 1, 1, (hipStream_t)stream, nullptr, nullptr,
-                                 nullptr, yb, split, true, gsc);
-  SMSUT_REQUIRE(rc == 0);
-  SMSUT_LAUNCH_CHECK();
-  return SMSUT_OK;
+  ConvCall c = conv_call(x, w, ya, N, H, W, Kdim, Ndim, stream);
+  set_transposed(c, transposed);
+  c.y2 = yb; c.split = split; c.gsc = gsc; c.f16_operands = true;
+  return run(c);
 }
 int smsut_conv2d_dgrad_mfma_bwdstats_f16(const float* gy, const float* w, float* gz, float* stats, const float* y1,
                                          const float* mean, const float* rstd, const float* gamma, const float* beta,
@@ -3416,11 +3319,9 @@ int smsut_conv2d_dgrad_mfma_bwdstats_f16(const float* gy, const float* w, float*
   SMSUT_REQUIRE(gy && w && gz && stats && y1 && mean && rstd && gamma && beta && N > 0 && H > 0 && W > 0);
   SMSUT_REQUIRE(fwd_p_eligible(N, H, W, Kdim, Ndim));
   const BstRef b{y1, mean, rstd, gamma, beta, slope};
-  const int rc = select_fwd_p(gy, w, gz, N, H, W, Kdim, Ndim, 1, (hipStream_t)stream, stats, nullptr, &b, nullptr, 0, nullptr,
-                              nullptr, true, gsc);
-  SMSUT_REQUIRE(rc == 0);
-  SMSUT_LAUNCH_CHECK();
-  return SMSUT_OK;
+  ConvCall c = conv_call(gy, w, gz, N, H, W, Kdim, Ndim, stream);
+  c.stats = stats; c.bst = &b; c.gsc = gsc; c.transposed_w = true; c.f16_operands = true;
+  return run_p(c);
 }
 
 // 3x3 weight gradient with fp16 operands (conv_f16_wgrad): full 8x16-pixel tiles and whole 16-channel tiles only

@@ -115,7 +115,7 @@ __global__ void __launch_bounds__(TPB) __attribute__((amdgpu_waves_per_eu(1, 1))
 conv_wino_l(const float* __restrict__ x, const float* __restrict__ x2, const float* __restrict__ w, const float* __restrict__ wu,
             float* __restrict__ y,
             float* __restrict__ y2, int split, int N, int H, int W, int nch, int Ndim, int tiles_x, int tiles_img, int items_per_wg,
-            int transposed, float* __restrict__ stats, WinoBst bst, WinoAff aff, WinoSc sc, FinRef fin) {
+            int transposed, float* __restrict__ stats, BstRef bst, AffRef aff, ScRef sc, FinRef fin) {
   static_assert(!(BST && (STATS || ACC)), "BST excludes the forward statistics and the accumulate form");
   static_assert(!FIN || STATS || BST, "in-launch finalize (common.h): statistics / BST forms");
   static_assert(!INAFF || (STATS && !ACC && !BST && !DUAL), "input-side IN: forward statistics form only");
@@ -774,78 +774,79 @@ inline void allow_big_lds(size_t bytes) {
 
 constexpr int WINO_WGS_PER_CU = 1;
 
+// Launch sites name a form by its F_* bits (common.h); the kernel's own parameter list stays one bool per flag (bench.py's roofline
+// leg and profiles/summarize.py find the kernel in a trace by that list).
+template <int NTN, unsigned F>
+constexpr auto wino_l_kernel = conv_wino_l<NTN, (F & F_STATS) != 0, (F & F_ACC) != 0, (F & F_BST) != 0, (F & F_DUAL) != 0,
+                                           (F & F_INAFF) != 0, (F & F_SC) != 0, (F & F_SC2) != 0, (F & F_PRE) != 0, (F & F_FIN) != 0>;
+
 template <int NTN>
-int launch_ntn(const float* x, const float* x2, const float* w, const float* wu, float* y, float* y2, int split, int N, int H, int W,
-               int Kdim, int Ndim, int transposed, float* stats, const WinoBst* bst, const WinoAff* aff, const WinoSc* sc, hipStream_t st,
-               const FinRef* fin) {
-  const int tiles_x = W / TW, tiles_img = tiles_x * (H / TH);
-  if (fin && (!fin->tickets || !fin->o0 || !fin->o1 || !stats || y2 || (transposed & 2) ||
-              (fin->s0 && !(sc && !(transposed & 1) && sc->stats && fin->s1)) || (!fin->s0 && sc)))
+int launch_ntn(const ConvCall& c) {
+  const bool tw = c.transposed_w, acc = c.accumulate;
+  const auto x2 = c.x2; const auto y2 = c.y2; const auto stats = c.stats;
+  const auto bst = c.bst; const auto aff = c.aff; const auto sc = c.sc; const auto fin = c.fin;
+  const int tiles_x = c.W / TW, tiles_img = tiles_x * (c.H / TH);
+  if (fin && (!fin->tickets || !fin->o0 || !fin->o1 || !stats || y2 || acc ||
+              (fin->s0 && !(sc && !tw && sc->stats && fin->s1)) || (!fin->s0 && sc)))
     return -1;
-  const FinRef fv = fin ? *fin : FinRef{};
-  const int nz = Ndim / (16 * NTN);
-  const int64_t items = (int64_t)N * tiles_img;
+  const int nz = c.Ndim / (16 * NTN);
+  const int64_t items = (int64_t)c.N * tiles_img;
   // resident workgroups per CU: ONE (one wave per SIMD: registers, 2 LDS buffers)
   const int64_t slots = (int64_t)device_cus() * WINO_WGS_PER_CU;
   int ipw = (int)((items * nz + slots - 1) / slots);
   if (ipw < 1) ipw = 1;
   dim3 grid((unsigned)((items + ipw - 1) / ipw), nz);
-  const int nch = Kdim / 16;
-  const WinoBst bv = bst ? *bst : WinoBst{};
-  const WinoAff av = aff ? *aff : WinoAff{};
-  const WinoSc sv = sc ? *sc : WinoSc{};
-  const bool sc2 = sc && (transposed & 1), scf = sc && !sc2;
+  const int nch = c.Kdim / 16;
+  const bool sc2 = sc && tw, scf = sc && !sc2;
+  // prepared weights (smsut_wino_prepare by the caller, passed with the call): copied by LDS-DMA instead of transformed per chunk
+  const float* const wu = sc2 ? nullptr : c.wu;
   const size_t sh = wino_l_lds<NTN>(scf, !aff && SMSUT_WINO_GLDS != 0);
-#define WGO2(ST, AC, BS, DU, IA, S1, S2, PR, FI)                                                                          \
-  do {                                                                                                                     \
-    allow_big_lds<conv_wino_l<NTN, ST, AC, BS, DU, IA, S1, S2, PR, FI>>(sh);                                               \
-    conv_wino_l<NTN, ST, AC, BS, DU, IA, S1, S2, PR, FI><<<grid, TPB, sh, st>>>(x, x2, w, wu, y, y2, split, N, H, W, nch,  \
-                                                                                Ndim, tiles_x, tiles_img, ipw, transposed, \
-                                                                                stats, bv, av, sv, fv);                    \
-  } while (0)
-#define WGO1(ST, AC, BS, DU, IA, S1, S2, PR)                                                                              \
-  do {                                                                                                                     \
-    if constexpr ((ST) || (BS)) {                                                                                          \
-      if (fin) { WGO2(ST, AC, BS, DU, IA, S1, S2, PR, true); break; }                                                      \
-    }                                                                                                                      \
-    WGO2(ST, AC, BS, DU, IA, S1, S2, PR, false);                                                                           \
-  } while (0)
-#define WGO(ST, AC, BS, DU, IA, S1, S2)                                                                                    \
-  do {                                                                                                                     \
-    if constexpr (!(S2)) {                                                                                                 \
-      if (wu) { WGO1(ST, AC, BS, DU, IA, S1, S2, true); break; }                                                           \
-    }                                                                                                                      \
-    WGO1(ST, AC, BS, DU, IA, S1, S2, false);                                                                               \
-  } while (0)
+  auto go = [&](auto form) {
+    constexpr auto kern = wino_l_kernel<NTN, decltype(form)::value>;
+    allow_big_lds<kern>(sh);
+    kern<<<grid, TPB, sh, c.stream>>>((const float*)c.x, x2, c.w, wu, (float*)c.y, y2, c.split, c.N, c.H, c.W, nch, c.Ndim, tiles_x,
+                                      tiles_img, ipw, c.transposed_bits(), stats, bst ? *bst : BstRef{}, aff ? *aff : AffRef{},
+                                      sc ? *sc : ScRef{}, fin ? *fin : FinRef{});
+    return 0;
+  };
+  // `form`, with the prepared-weights twin (every form but SC2) and the in-launch finalize (statistics / BST forms) chosen at run time
+  auto go_twins = [&](auto form) {
+    constexpr unsigned B = decltype(form)::value;
+    auto go_fin = [&](auto f) {
+      constexpr unsigned P = decltype(f)::value;
+      if constexpr ((P & (F_STATS | F_BST)) != 0) {
+        if (fin) return go(Form<P | F_FIN>{});
+      }
+      return go(f);
+    };
+    if constexpr (!(B & F_SC2)) {
+      if (wu) return go_fin(Form<B | F_PRE>{});
+    }
+    return go_fin(form);
+  };
   if (sc2) {
-    if (!x2 || !sc->w || stats || bst || aff || (transposed & 2) || nch % 2) return -1;
-    WGO(false, false, false, true, false, false, true);
+    if (!x2 || !sc->w || stats || bst || aff || acc || nch % 2) return -1;
+    return go_twins(Form<F_DUAL | F_SC2>{});
   } else if (scf) {
-    if (!stats || bst || aff || y2 || transposed || !sc->w || !sc->y || !sc->stats || (x2 && nch % 2)) return -1;
-    if (x2) WGO(true, false, false, true, false, true, false);
-    else WGO(true, false, false, false, false, true, false);
+    if (!stats || bst || aff || y2 || tw || acc || !sc->w || !sc->y || !sc->stats || (x2 && nch % 2)) return -1;
+    return x2 ? go_twins(Form<F_STATS | F_DUAL | F_SC>{}) : go_twins(Form<F_STATS | F_SC>{});
   } else if (aff) {
-    if (!stats || bst || y2 || x2 || transposed) return -1;
-    WGO(true, false, false, false, true, false, false);
+    if (!stats || bst || y2 || x2 || tw || acc) return -1;
+    return go_twins(Form<F_STATS | F_INAFF>{});
   } else if (x2) {
-    if (!stats || bst || y2 || transposed || nch % 2) return -1;
-    WGO(true, false, false, true, false, false, false);
+    if (!stats || bst || y2 || tw || acc || nch % 2) return -1;
+    return go_twins(Form<F_STATS | F_DUAL>{});
   } else if (bst) {
-    if (!stats || y2 || (transposed & 2)) return -1;
-    WGO(false, false, true, false, false, false, false);
-  } else if (transposed & 2) {
+    if (!stats || y2 || acc) return -1;
+    return go_twins(Form<F_BST>{});
+  } else if (acc) {
     if (stats) return -1;
-    WGO(false, true, false, false, false, false, false);
+    return go_twins(Form<F_ACC>{});
   } else if (stats) {
     if (y2) return -1;
-    WGO(true, false, false, false, false, false, false);
-  } else {
-    WGO(false, false, false, false, false, false, false);
+    return go_twins(Form<F_STATS>{});
   }
-#undef WGO
-#undef WGO1
-#undef WGO2
-  return 0;
+  return go_twins(Form<0u>{});
 }
 
 }  // namespace
@@ -855,21 +856,15 @@ bool smsut_wino_l_eligible(int N, int H, int W, int Kdim, int Ndim) {
          (int64_t)N * H * W * (Kdim > Ndim ? Kdim : Ndim) < (1ll << 31);
 }
 
-int smsut_wino_l_launch(const float* x, const float* x2, const float* w, float* y, float* y2, int split, int N, int H, int W,
-                        int Kdim, int Ndim, int transposed, float* stats, int* tiles_out, const WinoBst* bst, const WinoAff* aff,
-                        const WinoSc* sc, hipStream_t st, const float* wu_in, const FinRef* fin) {
-  if (!smsut_wino_l_eligible(N, H, W, Kdim, Ndim)) return -1;
-  if (y2 && (split <= 0 || split >= Ndim || split % 16 != 0 || (Ndim - split) % 16 != 0 || stats || bst)) return -1;
-  if (tiles_out) { *tiles_out = (W / TW) * (H / TH); return 0; }
+int smsut_wino_l_launch(const ConvCall& c) {
+  if (!smsut_wino_l_eligible(c.N, c.H, c.W, c.Kdim, c.Ndim)) return -1;
+  if (c.y2 && (c.split <= 0 || c.split >= c.Ndim || c.split % 16 != 0 || (c.Ndim - c.split) % 16 != 0 || c.stats || c.bst)) return -1;
+  if (c.tiles_out) { *c.tiles_out = (c.W / TW) * (c.H / TH); return 0; }
   // output-channel slabs per workgroup: two (one input transform feeds 32 channels, one wave per SIMD) when the grid still
   // fills the chip and no slab straddles a split
-  const int64_t items = (int64_t)N * (W / TW) * (H / TH);
-  const int ntn = (Ndim % 32 == 0 && !(y2 && split % 32 != 0) && items * (Ndim / 32) >= device_cus()) ? 2 : 1;
-  // prepared weights (smsut_wino_prepare by the caller, passed with the call): copied by LDS-DMA instead of transformed per chunk
-  const bool sc2 = sc && (transposed & 1);
-  const float* wu = sc2 ? nullptr : wu_in;
-  if (ntn == 2) return launch_ntn<2>(x, x2, w, wu, y, y2, split, N, H, W, Kdim, Ndim, transposed, stats, bst, aff, sc, st, fin);
-  return launch_ntn<1>(x, x2, w, wu, y, y2, split, N, H, W, Kdim, Ndim, transposed, stats, bst, aff, sc, st, fin);
+  const int64_t items = (int64_t)c.N * (c.W / TW) * (c.H / TH);
+  const bool two = c.Ndim % 32 == 0 && !(c.y2 && c.split % 32 != 0) && items * (c.Ndim / 32) >= device_cus();
+  return two ? launch_ntn<2>(c) : launch_ntn<1>(c);
 }
 
 extern "C" {
