@@ -190,6 +190,30 @@ struct ConvCall {
   int transposed_bits() const { return (transposed_w ? 1 : 0) | (accumulate ? 2 : 0); }
 };
 
+// ---- one description of a 3x3 / 1x1 weight-gradient launch (conv_mfma.hip, conv_wgrad_rr.hip) ---------------------------------------
+// gw [KS*KS (+ 1 with gs)][Cin][Cout] = sum_p x[p + tap] (x) gy[p]: every kernel writes one slab per split into `part`, sum_splits
+// adds them in a fixed order.  The shape and the forms are all that picks a kernel and its split count, so the planning queries
+// (`_supported`, `_ws`) ask with a WgradKey and no operand is made up for them.
+struct WgradKey { int N, H, W, Cin, Cout; bool cat, aff, sc; };
+// PAIRED launch (register-row kernel): the last n of the N images are a second set of tensors that went through the same conv, in
+// the same form (x2 / gs / statistics present in both sets or in neither); one slab set holds the sum over both.
+struct WgradSetB { const float* x; const float* x2; const float* gy; const float* gs; const float* mean; const float* rstd; int n; };
+struct WgradCall {
+  const void* x = nullptr;                // fp16 when x_f16
+  const float* x2 = nullptr;              // x is the virtual cat([x, x2]) with ca channels in x
+  int ca = 0;
+  const float* gy = nullptr;
+  const float* gs = nullptr;              // fused 1x1-shortcut weight gradient: slab row KS*KS = sum_p x[p] (x) gs[p]
+  const AffRef* aff = nullptr;            // x is the raw conv output, lrelu(IN(.)) applied in flight (zero padding after)
+  const float* gsc = nullptr;             // fp16 operands: {s, 1/s} of gy (and gs)
+  float* part = nullptr;                  // slab workspace [splits][rows][Cin][Cout]
+  int N = 0, H = 0, W = 0, Cin = 0, Cout = 0, KS = 3;
+  bool x_f16 = false;
+  hipStream_t stream = nullptr;
+  const WgradSetB* b = nullptr;
+  WgradKey key() const { return WgradKey{N, H, W, Cin, Cout, x2 != nullptr, aff != nullptr, gs != nullptr}; }
+};
+
 typedef unsigned long long smsut_u64;
 __device__ __forceinline__ void st_sc1_f2(float* p, float a, float b) {      // 8-byte write-through store
   const smsut_u64 bits = ((smsut_u64)__float_as_uint(b) << 32) | (smsut_u64)__float_as_uint(a);

@@ -2565,7 +2565,22 @@ conv_k4_wgrad(const float* __restrict__ x, const float* __restrict__ gy, float* 
   }
 }
 
-struct WgradPlan { int cit, cot, splits, tiles_per_split, tiles_x, tiles_y; };
+// ---- weight gradient: plan, kernel ladder (families in the order wgrad_select tries them) and launchers -----------------------------
+enum WgradFamily {
+  WF_NONE,     // no kernel for this shape and form
+  WF_RR,       // register-row kernel (conv_wgrad_rr.hip): no LDS staging, no barrier in the main loop
+  WF_PLANE,    // plane_wgrad: whole-batch GEMM of a tiny plane, final values written directly (no slabs)
+  WF_C8,       // row-split kernel, 8-channel form (tap pairs share an accumulator tile) ...
+  WF_C8_SC,    // ... with the fused shortcut
+  WF_TS,       // tap-split kernel (32 x 32 channel slabs, full tiles)
+  WF_ROWS,     // row-split kernel conv_mfma_wgrad<KS, cit, cot>
+};
+struct WgradPlan {
+  int cit, cot, splits, tiles_per_split, tiles_x, tiles_y;     // splits: slabs the launch writes
+  WgradFamily fam = WF_NONE;
+  int rows = 0;           // tap rows of a slab: KS*KS, + 1 with the fused shortcut
+  int ws_splits = 0;      // slabs a workspace must hold: the MAXIMUM of the register-row rung's and of the rung below it (below_rr)
+};
 
 constexpr int WGRAD_TARGET11 = 768;     // workgroups the split plan aims for: 16 x 16 slabs ...
 constexpr int WGRAD_TARGET = 512;       // ... and the wider ones
@@ -2599,10 +2614,55 @@ WgradPlan plan_wgrad(int N, int H, int W, int Cin, int Cout) {
   return p;
 }
 
+#ifndef PLANE_WGRAD_MAX_HW
+#define PLANE_WGRAD_MAX_HW 64      // 8x8 planes too: 57 -> 35 us at B16 256->256 vs the tap-split kernel (scratch/plane_wgrad_ab.py)
+#endif
+// planes small enough for the whole-batch GEMM form
+inline bool plane_wgrad_applies(int N, int H, int W, int Cin, int Cout) {
+  return H * W <= PLANE_WGRAD_MAX_HW && W % 4 == 0 && Cin % 32 == 0 && Cout % 32 == 0 && (int64_t)N * H * W <= 4096 &&
+         (int64_t)N * H * W * (Cin > Cout ? Cin : Cout) < (1ll << 31);
+}
+inline bool wgrad_channels_ok(int Cin, int Cout) { return Cin >= 4 && (Cin % 4) == 0 && Cout >= 4 && (Cout % 4) == 0; }
+
+// THE kernel ladder of the fp32 weight gradient: the launch (wgrad_run) and every `_supported` / `_ws` query read this one plan, so
+// no launch writes more slabs than its caller was told to allocate.  below_rr: the ladder under the register-row rung, where a call
+// continues when that launcher declines.  WF_NONE / WF_PLANE plans keep the row-split tile split: the `_ws` queries answer for them too.
+WgradPlan wgrad_select(const WgradKey& k, int KS, bool below_rr = false) {
+  if (k.N <= 0 || k.H <= 0 || k.W <= 0) return WgradPlan{};
+  WgradPlan p = plan_wgrad(k.N, k.H, k.W, k.Cin, k.Cout);
+  p.rows = KS * KS + (k.sc ? 1 : 0);
+  p.ws_splits = p.splits;
+  if ((KS != 1 && KS != 3) || !wgrad_channels_ok(k.Cin, k.Cout)) return p;
+  if ((k.aff && (k.cat || k.sc)) || (KS == 1 && (k.aff || k.sc))) return p;      // forms no kernel has
+  if (KS == 1) { p.fam = WF_ROWS; return p; }
+  const int rr = smsut_wgrad_rr_splits(k);               // the register-row kernel plans its own split count
+  if (rr > p.ws_splits) p.ws_splits = rr;
+  if (rr && !below_rr) { p.fam = WF_RR; p.splits = rr; return p; }
+  if (plane_wgrad_applies(k.N, k.H, k.W, k.Cin, k.Cout) && !k.aff) {
+    if (!k.sc) p.fam = WF_PLANE;
+    return p;
+  }
+  if (k.Cin == 8 && !k.cat && !k.aff) {                  // (fused shortcut: up to two 16-channel result tiles)
+    p.fam = !k.sc ? WF_C8 : k.Cout <= 32 ? WF_C8_SC : WF_NONE;
+    return p;
+  }
+  // whole 32 x 32 channel slabs, full tiles: the fused shortcut wins 6-14 us per call there; on the 16-channel slabs it pushed the
+  // row-split kernel over 256 VGPRs and ran 0-7 us SLOWER (scratch/wsc_ab.py): two kernels, unless the register-row kernel takes them
+  if (k.H % WTH == 0 && k.W % TW == 0 && k.Cin % 32 == 0 && k.Cout % 32 == 0 &&
+      (int64_t)k.N * k.H * k.W * (k.Cin > k.Cout ? k.Cin : k.Cout) < (1ll << 31))
+    p.fam = WF_TS;
+  else if (!k.sc) p.fam = WF_ROWS;
+  return p;
+}
+inline int64_t wgrad_ws_floats(const WgradKey& k, int KS) {
+  const WgradPlan p = wgrad_select(k, KS);
+  return (int64_t)p.ws_splits * p.rows * k.Cin * k.Cout;
+}
+
+// row-split kernel; the form follows the call and the plan's family.  -1: no instantiation (nothing launched).  up = 2
+// (ConvTranspose2x2 only): gy is the 2x larger tensor, up * up tap groups in blockIdx.y
 template <int KS, int CIT, int COT>
-int launch_wgrad(const float* x, const float* gy, float* part, int N, int H, int W, int Cin, int Cout,
-                 const WgradPlan& p, int gsc, int ntaps, hipStream_t st, const float* x2 = nullptr, int ca = 0,
-                 const AffRef* aff = nullptr, bool c8 = false, const float* gs = nullptr) {
+int launch_wgrad(const WgradCall& c, const WgradPlan& p, int up) {
   constexpr int IH = WTH + KS - 1, IW = TW + KS - 1;
   constexpr int CI_T = 16 * CIT, CO_T = 16 * COT;
   constexpr int SI = (CI_T % 32 == 16) ? CI_T : CI_T + 16;
@@ -2611,39 +2671,140 @@ int launch_wgrad(const float* x, const float* gy, float* part, int N, int H, int
   constexpr size_t red = (size_t)KS * KS * CIT * COT * 64 * 4 * sizeof(float);
   constexpr size_t sh = stage > red ? stage : red;
   static_assert(sh <= 64 * 1024, "LDS budget");
-  const int nci = (Cin + CI_T - 1) / CI_T;
-  dim3 grid(p.splits, nci * ntaps, (Cout + CO_T - 1) / CO_T);
-  if (gs && !c8) return -1;
-  if (c8 && gs) {                                 // fused shortcut weight gradient of the 8-channel form (SC8)
+  const int nci = (c.Cin + CI_T - 1) / CI_T;
+  const dim3 grid(p.splits, nci * up * up, (c.Cout + CO_T - 1) / CO_T);
+  auto go = [&](auto kern, size_t lds) {
+    kern<<<grid, TPB, lds, c.stream>>>((const float*)c.x, c.gy, c.part, c.N, c.H, c.W, c.Cin, c.Cout, p.tiles_x, p.tiles_y,
+                                       p.tiles_per_split, up, nci, c.x2, c.ca, c.aff ? *c.aff : AffRef{}, c.gs);
+    return 0;
+  };
+  const bool c8 = p.fam == WF_C8 || p.fam == WF_C8_SC;
+  if (c.gs && p.fam != WF_C8_SC) return -1;
+  if (c8) {
     if constexpr (KS == 3 && CIT == 1) {
       constexpr size_t stage_sc = (size_t)(IH * IW * SI + 2 * WTH * TW * SO) * sizeof(float);
       constexpr size_t red_sc = (size_t)((KS * KS + 1) / 2 + 1) * CIT * COT * 64 * 4 * sizeof(float);
       constexpr size_t sh_sc = stage_sc > red_sc ? stage_sc : red_sc;
       static_assert(sh_sc <= 64 * 1024, "LDS budget");
-      if (aff || x2 || gsc != 1 || ntaps != 1 || Cin != 8) return -1;
-      conv_mfma_wgrad<KS, CIT, COT, false, false, true, true><<<grid, TPB, sh_sc, st>>>(x, gy, part, N, H, W, Cin, Cout, p.tiles_x,
-                                                                                    p.tiles_y, p.tiles_per_split, 1, nci, nullptr, 0,
-                                                                                    AffRef{}, gs);
-      return 0;
+      if (c.aff || c.x2 || up != 1 || c.Cin != 8) return -1;
+      return c.gs ? go(conv_mfma_wgrad<KS, CIT, COT, false, false, true, true>, sh_sc)
+                  : go(conv_mfma_wgrad<KS, CIT, COT, false, false, true>, sh);
     } else return -1;
   }
-  if (c8) {
-    if constexpr (KS == 3 && CIT == 1) {
-      if (aff || x2 || gsc != 1 || Cin != 8) return -1;
-      conv_mfma_wgrad<KS, CIT, COT, false, false, true><<<grid, TPB, sh, st>>>(x, gy, part, N, H, W, Cin, Cout, p.tiles_x,
-                                                                              p.tiles_y, p.tiles_per_split, gsc, nci, nullptr, 0);
-    } else return -1;
-  } else if (aff) {
-    if (x2 || gsc != 1) return -1;
-    conv_mfma_wgrad<KS, CIT, COT, false, true><<<grid, TPB, sh, st>>>(x, gy, part, N, H, W, Cin, Cout, p.tiles_x, p.tiles_y,
-                                                                     p.tiles_per_split, gsc, nci, nullptr, 0, *aff);
-  } else if (x2)
-    conv_mfma_wgrad<KS, CIT, COT, true><<<grid, TPB, sh, st>>>(x, gy, part, N, H, W, Cin, Cout, p.tiles_x, p.tiles_y,
-                                                              p.tiles_per_split, gsc, nci, x2, ca);
-  else
-    conv_mfma_wgrad<KS, CIT, COT, false><<<grid, TPB, sh, st>>>(x, gy, part, N, H, W, Cin, Cout, p.tiles_x, p.tiles_y,
-                                                               p.tiles_per_split, gsc, nci, nullptr, 0);
-  return 0;
+  if (c.aff) return (c.x2 || up != 1) ? -1 : go(conv_mfma_wgrad<KS, CIT, COT, false, true>, sh);
+  return c.x2 ? go(conv_mfma_wgrad<KS, CIT, COT, true>, sh) : go(conv_mfma_wgrad<KS, CIT, COT, false>, sh);
+}
+int launch_wgrad_rows(const WgradCall& c, const WgradPlan& p, int up = 1) {
+  if (c.KS == 1)
+    return p.cit == 1 ? (p.cot == 1 ? launch_wgrad<1, 1, 1>(c, p, up) : launch_wgrad<1, 1, 2>(c, p, up))
+                      : (p.cot == 1 ? launch_wgrad<1, 2, 1>(c, p, up) : launch_wgrad<1, 2, 2>(c, p, up));
+  return p.cit == 1 ? (p.cot == 1 ? launch_wgrad<3, 1, 1>(c, p, up) : launch_wgrad<3, 1, 2>(c, p, up))
+                    : (p.cot == 1 ? launch_wgrad<3, 2, 1>(c, p, up) : launch_wgrad<3, 2, 2>(c, p, up));
+}
+
+// tap-split kernel: {cat, aff, sc} of the call -> conv_mfma_wgrad_ts<DUAL, INAFF, SC>
+int launch_wgrad_ts(const WgradCall& c, const WgradPlan& p) {
+  constexpr size_t sh = (size_t)((WTH + 2) * (TW + 2) * WTS_STRIDE + WTH * TW * WTS_STRIDE + 4) * sizeof(float);
+  constexpr size_t sh_sc = (size_t)((WTH + 2) * (TW + 2) * WTS_STRIDE + WTH * TW * WTS_STRIDE_SC + 4) * sizeof(float);
+  const dim3 grid(p.splits, c.Cin / 32, c.Cout / 32);
+  auto go = [&](auto kern, size_t lds) {
+    kern<<<grid, TPB, lds, c.stream>>>((const float*)c.x, c.gy, c.part, c.N, c.H, c.W, c.Cin, c.Cout, p.tiles_x, p.tiles_y,
+                                       p.tiles_per_split, c.x2, c.ca, c.aff ? *c.aff : AffRef{}, c.gs);
+    return 0;
+  };
+  if (c.gs) {
+    if (c.aff) return -1;
+    [[maybe_unused]] static const bool attr = [] {       // (once: the shortcut forms' LDS tile is over the 64 KB default)
+      (void)hipFuncSetAttribute((const void*)conv_mfma_wgrad_ts<false, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh_sc);
+      (void)hipFuncSetAttribute((const void*)conv_mfma_wgrad_ts<true, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh_sc);
+      return true;
+    }();
+    return c.x2 ? go(conv_mfma_wgrad_ts<true, false, true>, sh_sc) : go(conv_mfma_wgrad_ts<false, false, true>, sh_sc);
+  }
+  if (c.aff) return c.x2 ? -1 : go(conv_mfma_wgrad_ts<false, true>, sh);
+  return c.x2 ? go(conv_mfma_wgrad_ts<true>, sh) : go(conv_mfma_wgrad_ts<false>, sh);
+}
+
+// what every weight-gradient entry point shares: the operands (x2 nullable: ca then counts for nothing), shape and stream of a call ...
+inline WgradCall wgrad_call(const void* x, const float* x2, int ca, const float* gy, float* part, int N, int H, int W, int Cin, int Cout,
+                            void* stream) {
+  WgradCall c;
+  c.x = x; c.x2 = x2; c.ca = x2 ? ca : 0; c.gy = gy; c.part = part;
+  c.N = N; c.H = H; c.W = W; c.Cin = Cin; c.Cout = Cout; c.stream = (hipStream_t)stream;
+  return c;
+}
+// ... and its end: rc of a launcher (-1 = form not covered, nothing launched), then the plan's slabs summed into gw in a fixed order
+inline int wgrad_reduce(int rc, const WgradCall& c, const WgradPlan& p, float* gw) {
+  SMSUT_REQUIRE(rc == 0);
+  launch_sum_splits(c.part, gw, p.rows * c.Cin * c.Cout, p.splits, c.stream);
+  SMSUT_LAUNCH_CHECK();
+  return SMSUT_OK;
+}
+
+// One fp32 weight-gradient call down the ladder.  gw null (measurement entry points): stop before the reduction and return the slab
+// count.  Paired and measurement calls are the register-row kernel's alone.
+int wgrad_run(const WgradCall& c, float* gw) {
+  SMSUT_REQUIRE(c.x && c.gy && c.part && c.N > 0 && c.H > 0 && c.W > 0);
+  SMSUT_REQUIRE(!c.x2 || (c.ca > 0 && c.ca < c.Cin && c.ca % 16 == 0 && (c.Cin - c.ca) % 4 == 0));
+  const WgradKey k = c.key();
+  WgradPlan p = wgrad_select(k, c.KS);
+  if (p.fam == WF_RR && smsut_wgrad_rr_launch(c) != 0) p = wgrad_select(k, c.KS, /*below_rr=*/true);   // declined: on down the ladder
+  if (c.b || !gw) SMSUT_REQUIRE(p.fam == WF_RR);
+  if (!gw) return hipGetLastError() == hipSuccess ? p.splits : SMSUT_EINVAL;
+  switch (p.fam) {
+    case WF_NONE: return SMSUT_EINVAL;
+    case WF_RR: return wgrad_reduce(0, c, p, gw);
+    case WF_TS: return wgrad_reduce(launch_wgrad_ts(c, p), c, p, gw);
+    case WF_PLANE:                                       // final values written directly: no split-slab sum
+      plane_wgrad<<<dim3(c.Cin / 32, c.Cout / 32, 9), TPB, 0, c.stream>>>((const float*)c.x, c.gy, gw, c.N, c.H, c.W, c.Cin, c.Cout,
+                                                                        c.x2, c.ca);
+      SMSUT_LAUNCH_CHECK();
+      return SMSUT_OK;
+    default: return wgrad_reduce(launch_wgrad_rows(c, p), c, p, gw);
+  }
+}
+
+// ---- fp16-operand 3x3 weight gradient (conv_f16_wgrad): full 8x16-pixel tiles and whole 16-channel tiles only -----------------------
+inline bool wgrad_f16_shape_ok(int N, int H, int W, int Cin, int Cout) {
+  return N > 0 && H > 0 && W > 0 && H % WTH == 0 && W % TW == 0 && Cin % 16 == 0 && Cout % 16 == 0 &&
+         (int64_t)N * H * W * (Cin > Cout ? Cin : Cout) < (1ll << 31);
+}
+WgradPlan plan_wgrad_f16(int N, int H, int W, int Cin, int Cout, bool sc) {
+  WgradPlan p = plan_wgrad(N, H, W, Cin, Cout);
+  p.cit = (Cin % 32 == 0) ? 2 : 1;
+  p.cot = (Cout % 32 == 0) ? 2 : 1;
+  p.rows = sc ? 10 : 9;
+  return p;
+}
+// forms: plain / virtual cat, each with the fused shortcut (10 tap rows); fp16 x (x_f16), plain or with the input-side IN
+template <int CI, int CO>
+int launch_wgrad_f16(const WgradCall& c, const WgradPlan& p) {
+  constexpr int NPX = (WTH + 2) * (TW + 2), NPG = WTH * TW;
+  const bool sc = c.gs != nullptr;
+  const size_t stage = (size_t)((CI * NPX + (sc ? 2 : 1) * CO * NPG) * 16 + 8) * sizeof(_Float16);
+  const size_t red = (CI == 2 && CO == 2) ? 0 : (size_t)p.rows * CI * CO * 64 * 4 * sizeof(float);
+  const dim3 grid(p.splits, c.Cin / (16 * CI), c.Cout / (16 * CO));
+  auto go = [&](auto kern) {
+    kern<<<grid, TPB, stage > red ? stage : red, c.stream>>>((const float*)c.x, c.gy, c.part, c.N, c.H, c.W, c.Cin, c.Cout, p.tiles_x,
+                                                             p.tiles_y, p.tiles_per_split, c.x2, c.ca, c.gsc, c.gs,
+                                                             c.aff ? *c.aff : AffRef{});
+    return 0;
+  };
+  if (c.x_f16) {
+    if (c.x2 || sc) return -1;
+    return c.aff ? go(conv_f16_wgrad<CI, CO, false, false, true, true>) : go(conv_f16_wgrad<CI, CO, false, false, true>);
+  }
+  if (c.aff) return -1;
+  if (sc) return c.x2 ? go(conv_f16_wgrad<CI, CO, true, true>) : go(conv_f16_wgrad<CI, CO, false, true>);
+  return c.x2 ? go(conv_f16_wgrad<CI, CO, true, false>) : go(conv_f16_wgrad<CI, CO, false, false>);
+}
+int wgrad_f16_run(const WgradCall& c, float* gw) {
+  SMSUT_REQUIRE(c.x && c.gy && gw && c.part && wgrad_f16_shape_ok(c.N, c.H, c.W, c.Cin, c.Cout));
+  SMSUT_REQUIRE(!c.x2 || (c.ca > 0 && c.ca < c.Cin && c.ca % 16 == 0));
+  const WgradPlan p = plan_wgrad_f16(c.N, c.H, c.W, c.Cin, c.Cout, c.gs != nullptr);
+  const int rc = p.cit == 2 ? (p.cot == 2 ? launch_wgrad_f16<2, 2>(c, p) : launch_wgrad_f16<2, 1>(c, p))
+                            : (p.cot == 2 ? launch_wgrad_f16<1, 2>(c, p) : launch_wgrad_f16<1, 1>(c, p));
+  return wgrad_reduce(rc, c, p, gw);
 }
 
 // ---- what every conv entry point below shares ------------------------------------------------------------------------------------
@@ -3054,110 +3215,21 @@ int smsut_conv2d_fwd_mfma_cfg(const float* x, const float* w, float* y, int N, i
 }
 
 int smsut_conv2d_wgrad_mfma_supported(int KS, int stride, int pad, int Cin, int Cout) {
-  return (KS == 1 || KS == 3) && stride == 1 && pad == (KS - 1) / 2 && Cin >= 4 && (Cin % 4) == 0 && Cout >= 4 &&
-         (Cout % 4) == 0;
+  return (KS == 1 || KS == 3) && stride == 1 && pad == (KS - 1) / 2 && wgrad_channels_ok(Cin, Cout);
 }
 
-// workspace floats: splits * KS*KS*Cin*Cout
+// workspace floats: splits * KS*KS*Cin*Cout.  Serves the plain, virtual-cat and input-side-IN forms, which plan the same splits.
 int64_t smsut_conv2d_wgrad_mfma_ws(int N, int H, int W, int Cin, int Cout, int KS) {
-  const WgradPlan p = plan_wgrad(N, H, W, Cin, Cout);
-  int64_t need = (int64_t)p.splits * KS * KS * Cin * Cout;
-  if (KS == 3) {                                       // the register-row kernel (conv_wgrad_rr.hip) plans its own split count
-    const int64_t rr = (int64_t)smsut_wgrad_rr_splits(N, H, W, Cin, Cout, nullptr, 0, false, false) * 9 * Cin * Cout;
-    if (rr > need) need = rr;
-  }
-  return need;
+  return wgrad_ws_floats(WgradKey{N, H, W, Cin, Cout, false, false, false}, KS);
 }
 
 // gw [KS*KS][Cin][Cout] = sum over pixels of x (x) gy
-#ifndef PLANE_WGRAD_MAX_HW
-#define PLANE_WGRAD_MAX_HW 64      // 8x8 planes too: 57 -> 35 us at B16 256->256 vs the tap-split kernel (scratch/plane_wgrad_ab.py)
-#endif
-// planes small enough for the whole-batch GEMM form
-inline bool plane_wgrad_applies(int N, int H, int W, int Cin, int Cout) {
-  return H * W <= PLANE_WGRAD_MAX_HW && W % 4 == 0 && Cin % 32 == 0 && Cout % 32 == 0 && (int64_t)N * H * W <= 4096 &&
-         (int64_t)N * H * W * (Cin > Cout ? Cin : Cout) < (1ll << 31);
-}
-
-int smsut_conv2d_wgrad_sc_supported(int N, int H, int W, int Cin, int Cout);
-// gs != null (tap-split kernel shapes only): fused weight gradient of the block's 1x1 shortcut; gw and the slabs then have
-// KS*KS + 1 rows (row 9 = shortcut)
-static int wgrad_mfma_launch(const float* x, const float* gy, float* gw, float* workspace, int N, int H, int W, int Cin,
-                             int Cout, int KS, void* stream, const float* x2, int ca, const AffRef* aff = nullptr,
-                             const float* gs = nullptr) {
-  SMSUT_REQUIRE(x && gy && gw && workspace && N > 0 && H > 0 && W > 0);
-  SMSUT_REQUIRE(!gs || (KS == 3 && !aff && smsut_conv2d_wgrad_sc_supported(N, H, W, Cin, Cout)));
-  SMSUT_REQUIRE(smsut_conv2d_wgrad_mfma_supported(KS, 1, (KS - 1) / 2, Cin, Cout));
-  SMSUT_REQUIRE(!x2 || (ca > 0 && ca < Cin && ca % 16 == 0 && (Cin - ca) % 4 == 0));
-  SMSUT_REQUIRE(!aff || (KS == 3 && !x2));
-  hipStream_t st = (hipStream_t)stream;
-  if (KS == 3 && smsut_wgrad_rr_eligible(N, H, W, Cin, Cout, x2, ca, aff != nullptr, gs != nullptr)) {
-    // register-row kernel (conv_wgrad_rr.hip): no LDS staging, no barrier in the main loop
-    RrAff ra;
-    if (aff) ra = RrAff{aff->mean, aff->rstd, aff->gamma, aff->beta, aff->slope};
-    if (smsut_wgrad_rr_launch(x, x2, ca, gy, gs, workspace, N, H, W, Cin, Cout, aff ? &ra : nullptr, st) == 0) {
-      launch_sum_splits(workspace, gw, (9 + (gs ? 1 : 0)) * Cin * Cout,
-                        smsut_wgrad_rr_splits(N, H, W, Cin, Cout, x2, ca, aff != nullptr, gs != nullptr), st);
-      SMSUT_LAUNCH_CHECK();
-      return SMSUT_OK;
-    }
-  }
-  const WgradPlan p = plan_wgrad(N, H, W, Cin, Cout);
-  int rc = 0;                        // launch_wgrad: -1 = no kernel for this form (nothing was launched)
-  if (KS == 1) {
-    if (p.cit == 1 && p.cot == 1) rc = launch_wgrad<1, 1, 1>(x, gy, workspace, N, H, W, Cin, Cout, p, 1, 1, st, x2, ca);
-    else if (p.cit == 1) rc = launch_wgrad<1, 1, 2>(x, gy, workspace, N, H, W, Cin, Cout, p, 1, 1, st, x2, ca);
-    else if (p.cot == 1) rc = launch_wgrad<1, 2, 1>(x, gy, workspace, N, H, W, Cin, Cout, p, 1, 1, st, x2, ca);
-    else rc = launch_wgrad<1, 2, 2>(x, gy, workspace, N, H, W, Cin, Cout, p, 1, 1, st, x2, ca);
-  } else if (plane_wgrad_applies(N, H, W, Cin, Cout) && !aff) {
-    plane_wgrad<<<dim3(Cin / 32, Cout / 32, 9), TPB, 0, st>>>(x, gy, gw, N, H, W, Cin, Cout, x2, ca);
-    SMSUT_LAUNCH_CHECK();
-    return SMSUT_OK;                                 // final values written directly: no split-slab sum
-  } else {
-    const bool c8 = Cin == 8 && !x2 && !aff;                    // tap pairs share an accumulator tile
-    if (gs && !c8 && !(p.cit == 2 && p.cot == 2)) return SMSUT_EINVAL;     // (fused shortcut: 8-channel form or the tap-split kernel)
-    if (p.cit == 1 && p.cot == 1) rc = launch_wgrad<3, 1, 1>(x, gy, workspace, N, H, W, Cin, Cout, p, 1, 1, st, x2, ca, aff, c8, c8 ? gs : nullptr);
-    else if (p.cit == 1) rc = launch_wgrad<3, 1, 2>(x, gy, workspace, N, H, W, Cin, Cout, p, 1, 1, st, x2, ca, aff, c8, c8 ? gs : nullptr);
-    else if (p.cot == 1) rc = launch_wgrad<3, 2, 1>(x, gy, workspace, N, H, W, Cin, Cout, p, 1, 1, st, x2, ca, aff);
-    else if (H % WTH == 0 && W % TW == 0 && Cin % 32 == 0 && Cout % 32 == 0 &&
-             (int64_t)N * H * W * (Cin > Cout ? Cin : Cout) < (1ll << 31)) {
-      constexpr size_t sh = (size_t)((WTH + 2) * (TW + 2) * WTS_STRIDE + WTH * TW * WTS_STRIDE + 4) * sizeof(float);
-      dim3 grid(p.splits, Cin / 32, Cout / 32);
-      if (gs) {
-        constexpr size_t sh_sc = (size_t)((WTH + 2) * (TW + 2) * WTS_STRIDE + WTH * TW * WTS_STRIDE_SC + 4) * sizeof(float);
-        static bool attr = false;
-        if (!attr) {
-          (void)hipFuncSetAttribute((const void*)conv_mfma_wgrad_ts<false, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh_sc);
-          (void)hipFuncSetAttribute((const void*)conv_mfma_wgrad_ts<true, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh_sc);
-          attr = true;
-        }
-        if (x2)
-          conv_mfma_wgrad_ts<true, false, true><<<grid, TPB, sh_sc, st>>>(x, gy, workspace, N, H, W, Cin, Cout, p.tiles_x, p.tiles_y,
-                                                                         p.tiles_per_split, x2, ca, AffRef{}, gs);
-        else
-          conv_mfma_wgrad_ts<false, false, true><<<grid, TPB, sh_sc, st>>>(x, gy, workspace, N, H, W, Cin, Cout, p.tiles_x, p.tiles_y,
-                                                                          p.tiles_per_split, nullptr, 0, AffRef{}, gs);
-      } else if (aff)
-        conv_mfma_wgrad_ts<false, true><<<grid, TPB, sh, st>>>(x, gy, workspace, N, H, W, Cin, Cout, p.tiles_x, p.tiles_y,
-                                                               p.tiles_per_split, nullptr, 0, *aff);
-      else if (x2)
-        conv_mfma_wgrad_ts<true><<<grid, TPB, sh, st>>>(x, gy, workspace, N, H, W, Cin, Cout, p.tiles_x, p.tiles_y,
-                                                        p.tiles_per_split, x2, ca);
-      else
-        conv_mfma_wgrad_ts<false><<<grid, TPB, sh, st>>>(x, gy, workspace, N, H, W, Cin, Cout, p.tiles_x, p.tiles_y,
-                                                         p.tiles_per_split, nullptr, 0);
-    } else rc = launch_wgrad<3, 2, 2>(x, gy, workspace, N, H, W, Cin, Cout, p, 1, 1, st, x2, ca, aff);
-  }
-  if (rc != 0) return SMSUT_EINVAL;
-  const int wsize = (KS * KS + (gs ? 1 : 0)) * Cin * Cout;
-  launch_sum_splits(workspace, gw, wsize, p.splits, st);
-  SMSUT_LAUNCH_CHECK();
-  return SMSUT_OK;
-}
-
 int smsut_conv2d_wgrad_mfma(const float* x, const float* gy, float* gw, float* workspace, int N, int H, int W, int Cin,
                             int Cout, int KS, void* stream) {
-  return wgrad_mfma_launch(x, gy, gw, workspace, N, H, W, Cin, Cout, KS, stream, nullptr, 0);
+  SMSUT_REQUIRE(gw);
+  WgradCall c = wgrad_call(x, nullptr, 0, gy, workspace, N, H, W, Cin, Cout, stream);
+  c.KS = KS;
+  return wgrad_run(c, gw);
 }
 
 // 3x3 weight gradient whose x operand is lrelu(IN(x)) of the tensor passed (see smsut_conv2d_fwd_mfma_stats_inaff);
@@ -3165,9 +3237,11 @@ int smsut_conv2d_wgrad_mfma(const float* x, const float* gy, float* gw, float* w
 int smsut_conv2d_wgrad_mfma_inaff(const float* x, const float* gy, float* gw, float* workspace, const float* mean,
                                   const float* rstd, const float* gamma, const float* beta, float slope, int N, int H, int W,
                                   int Cin, int Cout, void* stream) {
-  SMSUT_REQUIRE(mean && rstd && gamma && beta);
+  SMSUT_REQUIRE(gw && mean && rstd && gamma && beta);
   const AffRef a{mean, rstd, gamma, beta, slope};
-  return wgrad_mfma_launch(x, gy, gw, workspace, N, H, W, Cin, Cout, 3, stream, nullptr, 0, &a);
+  WgradCall c = wgrad_call(x, nullptr, 0, gy, workspace, N, H, W, Cin, Cout, stream);
+  c.aff = &a;
+  return wgrad_run(c, gw);
 }
 
 // Measurement entry point (bench.py's roofline leg): the FIRST of the two launches of smsut_conv2d_wgrad_mfma_inaff alone -- the
@@ -3177,47 +3251,38 @@ int smsut_conv2d_wgrad_mfma_inaff(const float* x, const float* gy, float* gw, fl
 int smsut_conv2d_wgrad_mfma_slabs(const float* x, const float* gy, float* workspace, const float* mean, const float* rstd,
                                   const float* gamma, const float* beta, float slope, int N, int H, int W, int Cin, int Cout,
                                   void* stream) {
-  if (!x || !gy || !workspace || N <= 0 || H <= 0 || W <= 0) return SMSUT_EINVAL;
-  const bool aff = mean != nullptr;
-  if (aff && !(rstd && gamma && beta)) return SMSUT_EINVAL;
-  if (!smsut_wgrad_rr_eligible(N, H, W, Cin, Cout, nullptr, 0, aff, false)) return SMSUT_EINVAL;
-  const RrAff ra{mean, rstd, gamma, beta, slope};
-  if (smsut_wgrad_rr_launch(x, nullptr, 0, gy, nullptr, workspace, N, H, W, Cin, Cout, aff ? &ra : nullptr, (hipStream_t)stream) != 0)
-    return SMSUT_EINVAL;
-  if (hipGetLastError() != hipSuccess) return SMSUT_EINVAL;
-  return smsut_wgrad_rr_splits(N, H, W, Cin, Cout, nullptr, 0, aff, false);
+  SMSUT_REQUIRE(!mean || (rstd && gamma && beta));
+  const AffRef a{mean, rstd, gamma, beta, slope};
+  WgradCall c = wgrad_call(x, nullptr, 0, gy, workspace, N, H, W, Cin, Cout, stream);
+  c.aff = mean ? &a : nullptr;
+  return wgrad_run(c, nullptr);
 }
 
 // conv1's 3x3 weight gradient AND the 1x1 shortcut's (network/blocks.py:66-80: both convs read x) in one pass:
 //   gw10 [10][Cin][Cout]: rows 0..8 = sum_p x[p + tap] (x) gy[p]  (as smsut_conv2d_wgrad_mfma), row 9 = sum_p x[p] (x) gs[p].
 // xb nullable: non-null = x is the virtual cat([xa, xb]), ca channels in xa.  workspace: smsut_conv2d_wgrad_sc_ws floats.
 int smsut_conv2d_wgrad_sc_supported(int N, int H, int W, int Cin, int Cout) {
-  // the tap-split kernel's shapes (whole 32 x 32 channel slabs, full tiles): there the fusion wins 6-14 us per call.  On the
-  // 16-channel slabs (32->16, 16->32) the extra tile pushed the row-split kernel over 256 VGPRs and the pair ran 0-7 us SLOWER
-  // fused (scratch/wsc_ab.py) -- those keep the two-kernel form.
-  if (Cin == 8 && Cout >= 4 && Cout % 4 == 0 && Cout <= 32 && N > 0 && H > 0 && W > 0) return 1;   // 8-channel form (SC8)
-  // register-row kernel (conv_wgrad_rr.hip): one more accumulator tile per (ci tile, co tile) -- also on the 16-channel slabs
-  if (smsut_wgrad_rr_eligible(N, H, W, Cin, Cout, nullptr, 0, false, true)) return 1;
-  return N > 0 && H > 0 && W > 0 && H % WTH == 0 && W % TW == 0 && Cin % 32 == 0 && Cout % 32 == 0 &&
-         !plane_wgrad_applies(N, H, W, Cin, Cout) && (int64_t)N * H * W * (Cin > Cout ? Cin : Cout) < (1ll << 31);
+  return wgrad_select(WgradKey{N, H, W, Cin, Cout, false, false, true}, 3).fam != WF_NONE;
 }
 int64_t smsut_conv2d_wgrad_sc_ws(int N, int H, int W, int Cin, int Cout) {
-  const WgradPlan p = plan_wgrad(N, H, W, Cin, Cout);
-  const int rr = smsut_wgrad_rr_splits(N, H, W, Cin, Cout, nullptr, 0, false, true);
-  return (int64_t)(rr > p.splits ? rr : p.splits) * 10 * Cin * Cout;
+  return wgrad_ws_floats(WgradKey{N, H, W, Cin, Cout, false, false, true}, 3);
 }
 int smsut_conv2d_wgrad_mfma_sc(const float* xa, const float* xb, int ca, const float* gy, const float* gs, float* gw10,
                                float* workspace, int N, int H, int W, int Cin, int Cout, void* stream) {
-  SMSUT_REQUIRE(gs && smsut_conv2d_wgrad_sc_supported(N, H, W, Cin, Cout));
-  return wgrad_mfma_launch(xa, gy, gw10, workspace, N, H, W, Cin, Cout, 3, stream, xb, xb ? ca : 0, nullptr, gs);
+  SMSUT_REQUIRE(gw10 && gs);
+  WgradCall c = wgrad_call(xa, xb, ca, gy, workspace, N, H, W, Cin, Cout, stream);
+  c.gs = gs;
+  return wgrad_run(c, gw10);
 }
 
 // Weight gradient with x = the virtual cat([xa, xb]) (xa [N,H,W,ca], xb [N,H,W,Cin-ca], ca % 16 == 0) read in place;
 // workspace as smsut_conv2d_wgrad_mfma_ws(N, H, W, Cin, Cout, KS).
 int smsut_conv2d_wgrad_mfma_cat(const float* xa, const float* xb, int ca, const float* gy, float* gw, float* workspace,
                                 int N, int H, int W, int Cin, int Cout, int KS, void* stream) {
-  SMSUT_REQUIRE(xb);
-  return wgrad_mfma_launch(xa, gy, gw, workspace, N, H, W, Cin, Cout, KS, stream, xb, ca);
+  SMSUT_REQUIRE(gw && xb);
+  WgradCall c = wgrad_call(xa, xb, ca, gy, workspace, N, H, W, Cin, Cout, stream);
+  c.KS = KS;
+  return wgrad_run(c, gw);
 }
 
 // PAIRED 3x3 weight gradient (r05): gw = wgrad(set A) + wgrad(set B) in ONE launch of the register-row kernel, for two image sets
@@ -3228,33 +3293,30 @@ int smsut_conv2d_wgrad_mfma_cat(const float* xa, const float* xb, int ca, const 
 // rstd (x is the RAW conv output, lrelu(IN(.)) applied in flight: gamma, beta, slope shared -- same layer), gs (fused 1x1 shortcut,
 // gw holds 10 rows); each present in BOTH sets or in neither.
 int smsut_conv2d_wgrad_pair_supported(int NA, int NB, int H, int W, int Cin, int Cout, int cat, int aff, int sc) {
-  if (NA <= 0 || NB <= 0 || (cat && aff) || (aff && sc)) return 0;
-  if (sc && !smsut_conv2d_wgrad_sc_supported(NA + NB, H, W, Cin, Cout)) return 0;
-  return smsut_wgrad_rr_eligible(NA + NB, H, W, Cin, Cout, cat ? (const float*)1 : nullptr, cat ? Cin / 2 : 0, aff != 0, sc != 0) ? 1 : 0;
+  return NA > 0 && NB > 0 && wgrad_select(WgradKey{NA + NB, H, W, Cin, Cout, cat != 0, aff != 0, sc != 0}, 3).fam == WF_RR;
 }
 int64_t smsut_conv2d_wgrad_pair_ws(int NA, int NB, int H, int W, int Cin, int Cout, int cat, int aff, int sc) {
-  return (int64_t)smsut_wgrad_rr_splits(NA + NB, H, W, Cin, Cout, cat ? (const float*)1 : nullptr, cat ? Cin / 2 : 0, aff != 0, sc != 0) *
-         (sc ? 10 : 9) * Cin * Cout;
+  return (int64_t)smsut_wgrad_rr_splits(WgradKey{NA + NB, H, W, Cin, Cout, cat != 0, aff != 0, sc != 0}) * (sc ? 10 : 9) * Cin * Cout;
+}
+// what the paired entry point and its measurement twin share: one call over NA + NB images (the launcher checks set B against set A)
+static int wgrad_pair_run(const WgradSetB& sa, const WgradSetB& sb, int ca, const float* gamma, const float* beta, float slope, float* gw,
+                          float* workspace, int H, int W, int Cin, int Cout, void* stream) {
+  const bool aff = sa.mean != nullptr;
+  SMSUT_REQUIRE(aff == (sa.rstd != nullptr) && (!aff || (gamma && beta)));
+  const AffRef a{sa.mean, sa.rstd, gamma, beta, slope};
+  WgradCall c = wgrad_call(sa.x, sa.x2, ca, sa.gy, workspace, sa.n + sb.n, H, W, Cin, Cout, stream);
+  c.gs = sa.gs;
+  c.aff = aff ? &a : nullptr;
+  c.b = &sb;
+  return wgrad_run(c, gw);
 }
 int smsut_conv2d_wgrad_pair(const float* xA, const float* x2A, const float* gyA, const float* gsA, const float* meanA,
                             const float* rstdA, int NA, const float* xB, const float* x2B, const float* gyB, const float* gsB,
                             const float* meanB, const float* rstdB, int NB, int ca, const float* gamma, const float* beta, float slope,
                             float* gw, float* workspace, int H, int W, int Cin, int Cout, void* stream) {
-  SMSUT_REQUIRE(xA && gyA && xB && gyB && gw && workspace);
-  SMSUT_REQUIRE((x2A != nullptr) == (x2B != nullptr) && (gsA != nullptr) == (gsB != nullptr));
-  const bool aff = meanA != nullptr;
-  SMSUT_REQUIRE(aff == (rstdA != nullptr) && aff == (meanB != nullptr) && aff == (rstdB != nullptr) && (!aff || (gamma && beta)));
-  SMSUT_REQUIRE(smsut_conv2d_wgrad_pair_supported(NA, NB, H, W, Cin, Cout, x2A != nullptr, aff, gsA != nullptr));
-  SMSUT_REQUIRE(!x2A || (ca > 0 && ca < Cin && ca % 16 == 0));
-  hipStream_t st = (hipStream_t)stream;
-  const RrAff ra{meanA, rstdA, gamma, beta, slope};
-  const RrSetB sb{xB, x2B, gyB, gsB, meanB, rstdB, NB};
-  if (smsut_wgrad_rr_launch(xA, x2A, x2A ? ca : 0, gyA, gsA, workspace, NA + NB, H, W, Cin, Cout, aff ? &ra : nullptr, st, &sb) != 0)
-    return SMSUT_EINVAL;
-  launch_sum_splits(workspace, gw, (gsA ? 10 : 9) * Cin * Cout,
-                    smsut_wgrad_rr_splits(NA + NB, H, W, Cin, Cout, x2A, x2A ? ca : 0, aff, gsA != nullptr), st);
-  SMSUT_LAUNCH_CHECK();
-  return SMSUT_OK;
+  SMSUT_REQUIRE(gw);
+  return wgrad_pair_run(WgradSetB{xA, x2A, gyA, gsA, meanA, rstdA, NA}, WgradSetB{xB, x2B, gyB, gsB, meanB, rstdB, NB}, ca, gamma, beta,
+                        slope, gw, workspace, H, W, Cin, Cout, stream);
 }
 
 // Measurement entry point (bench.py's roofline leg), the paired twin of smsut_conv2d_wgrad_mfma_slabs: the register-row kernel of
@@ -3263,16 +3325,8 @@ int smsut_conv2d_wgrad_pair(const float* xA, const float* x2A, const float* gyA,
 int smsut_conv2d_wgrad_pair_slabs(const float* xA, const float* gyA, const float* meanA, const float* rstdA, int NA, const float* xB,
                                   const float* gyB, const float* meanB, const float* rstdB, int NB, const float* gamma,
                                   const float* beta, float slope, float* workspace, int H, int W, int Cin, int Cout, void* stream) {
-  if (!xA || !gyA || !xB || !gyB || !workspace) return SMSUT_EINVAL;
-  const bool aff = meanA != nullptr;
-  if (aff != (rstdA != nullptr) || aff != (meanB != nullptr) || aff != (rstdB != nullptr) || (aff && !(gamma && beta))) return SMSUT_EINVAL;
-  if (!smsut_conv2d_wgrad_pair_supported(NA, NB, H, W, Cin, Cout, 0, aff, 0)) return SMSUT_EINVAL;
-  const RrAff ra{meanA, rstdA, gamma, beta, slope};
-  const RrSetB sb{xB, nullptr, gyB, nullptr, meanB, rstdB, NB};
-  if (smsut_wgrad_rr_launch(xA, nullptr, 0, gyA, nullptr, workspace, NA + NB, H, W, Cin, Cout, aff ? &ra : nullptr, (hipStream_t)stream, &sb) != 0)
-    return SMSUT_EINVAL;
-  if (hipGetLastError() != hipSuccess) return SMSUT_EINVAL;
-  return smsut_wgrad_rr_splits(NA + NB, H, W, Cin, Cout, nullptr, 0, aff, false);
+  return wgrad_pair_run(WgradSetB{xA, nullptr, gyA, nullptr, meanA, rstdA, NA}, WgradSetB{xB, nullptr, gyB, nullptr, meanB, rstdB, NB}, 0,
+                        gamma, beta, slope, nullptr, workspace, H, W, Cin, Cout, stream);
 }
 
 // ---- fp16-operand entry points (BASELINE config 5; see the block comment above mfma16h) -----------------------------------
@@ -3325,121 +3379,46 @@ int smsut_conv2d_dgrad_mfma_bwdstats_f16(const float* gy, const float* w, float*
 }
 
 // 3x3 weight gradient with fp16 operands (conv_f16_wgrad): full 8x16-pixel tiles and whole 16-channel tiles only
-int smsut_conv2d_wgrad_f16_supported(int N, int H, int W, int Cin, int Cout) {
-  return N > 0 && H > 0 && W > 0 && H % WTH == 0 && W % TW == 0 && Cin % 16 == 0 && Cout % 16 == 0 &&
-         (int64_t)N * H * W * (Cin > Cout ? Cin : Cout) < (1ll << 31);
-}
-static WgradPlan plan_wgrad_f16(int N, int H, int W, int Cin, int Cout) {
-  WgradPlan p = plan_wgrad(N, H, W, Cin, Cout);
-  p.cit = (Cin % 32 == 0) ? 2 : 1;
-  p.cot = (Cout % 32 == 0) ? 2 : 1;
-  return p;
-}
+int smsut_conv2d_wgrad_f16_supported(int N, int H, int W, int Cin, int Cout) { return wgrad_f16_shape_ok(N, H, W, Cin, Cout); }
 int64_t smsut_conv2d_wgrad_f16_ws(int N, int H, int W, int Cin, int Cout) {
-  return (int64_t)plan_wgrad_f16(N, H, W, Cin, Cout).splits * 9 * Cin * Cout;
+  return (int64_t)plan_wgrad_f16(N, H, W, Cin, Cout, false).splits * 9 * Cin * Cout;
 }
-// x2 (nullable): x is the virtual cat([x, x2]) with ca channels in x (ca % 16 == 0).  gs != null: the fused-shortcut form (slab of
-// 10 tap rows, see conv_f16_wgrad<.., SC>).
-static void launch_wgrad_f16(const float* x, const float* x2, int ca, const float* gy, const float* gs, float* workspace,
-                             const float* gsc, int N, int H, int W, int Cin, int Cout, const WgradPlan& p, hipStream_t st,
-                             bool xh = false, const AffRef* aff = nullptr) {
-  constexpr int NPX = (WTH + 2) * (TW + 2), NPG = WTH * TW;
-#define F16_WGRAD(CI, CO, SCF)                                                                                              \
-  do {                                                                                                                      \
-    constexpr size_t stage = (size_t)((CI * NPX + (SCF ? 2 : 1) * CO * NPG) * 16 + 8) * sizeof(_Float16);                   \
-    constexpr size_t red = (CI == 2 && CO == 2) ? 0 : (size_t)(SCF ? 10 : 9) * CI * CO * 64 * 4 * sizeof(float);             \
-    constexpr size_t sh = stage > red ? stage : red;                                                                        \
-    dim3 grid(p.splits, Cin / (16 * CI), Cout / (16 * CO));                                                                 \
-    if (x2) conv_f16_wgrad<CI, CO, true, SCF><<<grid, TPB, sh, st>>>(x, gy, workspace, N, H, W, Cin, Cout, p.tiles_x,        \
-                                                                    p.tiles_y, p.tiles_per_split, x2, ca, gsc, gs);       \
-    else conv_f16_wgrad<CI, CO, false, SCF><<<grid, TPB, sh, st>>>(x, gy, workspace, N, H, W, Cin, Cout, p.tiles_x,          \
-                                                                  p.tiles_y, p.tiles_per_split, nullptr, 0, gsc, gs);    \
-  } while (0)
-#define F16_WGRAD_FORMS(SCF)                                  \
-  do {                                                        \
-    if (p.cit == 2 && p.cot == 2) F16_WGRAD(2, 2, SCF);       \
-    else if (p.cit == 2) F16_WGRAD(2, 1, SCF);                \
-    else if (p.cot == 2) F16_WGRAD(1, 2, SCF);                \
-    else F16_WGRAD(1, 1, SCF);                                \
-  } while (0)
-#define F16_WGRAD_XH(CI, CO)                                                                                                \
-  do {                                                                                                                      \
-    constexpr size_t stage = (size_t)((CI * NPX + CO * NPG) * 16 + 8) * sizeof(_Float16);                                   \
-    constexpr size_t red = (CI == 2 && CO == 2) ? 0 : (size_t)9 * CI * CO * 64 * 4 * sizeof(float);                         \
-    constexpr size_t sh = stage > red ? stage : red;                                                                        \
-    dim3 grid(p.splits, Cin / (16 * CI), Cout / (16 * CO));                                                                 \
-    if (aff)                                                                                                                \
-      conv_f16_wgrad<CI, CO, false, false, true, true><<<grid, TPB, sh, st>>>(x, gy, workspace, N, H, W, Cin, Cout, p.tiles_x, \
-                                                                             p.tiles_y, p.tiles_per_split, nullptr, 0, gsc,  \
-                                                                             nullptr, *aff);                               \
-    else                                                                                                                    \
-      conv_f16_wgrad<CI, CO, false, false, true><<<grid, TPB, sh, st>>>(x, gy, workspace, N, H, W, Cin, Cout, p.tiles_x,     \
-                                                                       p.tiles_y, p.tiles_per_split, nullptr, 0, gsc, nullptr); \
-  } while (0)
-  if (xh) {
-    if (p.cit == 2 && p.cot == 2) F16_WGRAD_XH(2, 2);
-    else if (p.cit == 2) F16_WGRAD_XH(2, 1);
-    else if (p.cot == 2) F16_WGRAD_XH(1, 2);
-    else F16_WGRAD_XH(1, 1);
-  } else if (gs) F16_WGRAD_FORMS(true);
-  else F16_WGRAD_FORMS(false);
-#undef F16_WGRAD_XH
-#undef F16_WGRAD_FORMS
-#undef F16_WGRAD
-}
+// x2 (nullable): x is the virtual cat([x, x2]) with ca channels in x (ca % 16 == 0)
 int smsut_conv2d_wgrad_f16(const float* x, const float* x2, int ca, const float* gy, float* gw, float* workspace,
                            const float* gsc, int N, int H, int W, int Cin, int Cout, void* stream) {
-  SMSUT_REQUIRE(x && gy && gw && workspace && smsut_conv2d_wgrad_f16_supported(N, H, W, Cin, Cout));
-  SMSUT_REQUIRE(!x2 || (ca > 0 && ca < Cin && ca % 16 == 0));
-  hipStream_t st = (hipStream_t)stream;
-  const WgradPlan p = plan_wgrad_f16(N, H, W, Cin, Cout);
-  launch_wgrad_f16(x, x2, ca, gy, nullptr, workspace, gsc, N, H, W, Cin, Cout, p, st);
-  launch_sum_splits(workspace, gw, 9 * Cin * Cout, p.splits, st);
-  SMSUT_LAUNCH_CHECK();
-  return SMSUT_OK;
+  WgradCall c = wgrad_call(x, x2, ca, gy, workspace, N, H, W, Cin, Cout, stream);
+  c.gsc = gsc;
+  return wgrad_f16_run(c, gw);
 }
 // ... with x stored as fp16 [N,H,W,Cin] (half storage: conv2's weight gradient of a BasicBlock reads the activated a1): same bits
 int smsut_conv2d_wgrad_f16_xh(const void* x16, const float* gy, float* gw, float* workspace, const float* gsc, int N, int H, int W,
                               int Cin, int Cout, void* stream) {
-  SMSUT_REQUIRE(x16 && gy && gw && workspace && smsut_conv2d_wgrad_f16_supported(N, H, W, Cin, Cout));
-  hipStream_t st = (hipStream_t)stream;
-  const WgradPlan p = plan_wgrad_f16(N, H, W, Cin, Cout);
-  launch_wgrad_f16((const float*)x16, nullptr, 0, gy, nullptr, workspace, gsc, N, H, W, Cin, Cout, p, st, true);
-  launch_sum_splits(workspace, gw, 9 * Cin * Cout, p.splits, st);
-  SMSUT_LAUNCH_CHECK();
-  return SMSUT_OK;
+  WgradCall c = wgrad_call(x16, nullptr, 0, gy, workspace, N, H, W, Cin, Cout, stream);
+  c.gsc = gsc; c.x_f16 = true;
+  return wgrad_f16_run(c, gw);
 }
 // ... with x the RAW fp16 conv1 output, lrelu(IN(.)) applied while staging (half-storage twin of smsut_conv2d_wgrad_mfma_inaff)
 int smsut_conv2d_wgrad_f16_xh_inaff(const void* y1_16, const float* gy, float* gw, float* workspace, const float* gsc,
                                     const float* mean, const float* rstd, const float* gamma, const float* beta, float slope, int N,
                                     int H, int W, int Cin, int Cout, void* stream) {
-  SMSUT_REQUIRE(y1_16 && gy && gw && workspace && mean && rstd && gamma && beta && smsut_conv2d_wgrad_f16_supported(N, H, W, Cin, Cout));
-  hipStream_t st = (hipStream_t)stream;
-  const WgradPlan p = plan_wgrad_f16(N, H, W, Cin, Cout);
+  SMSUT_REQUIRE(mean && rstd && gamma && beta);
   const AffRef a{mean, rstd, gamma, beta, slope};
-  launch_wgrad_f16((const float*)y1_16, nullptr, 0, gy, nullptr, workspace, gsc, N, H, W, Cin, Cout, p, st, true, &a);
-  launch_sum_splits(workspace, gw, 9 * Cin * Cout, p.splits, st);
-  SMSUT_LAUNCH_CHECK();
-  return SMSUT_OK;
+  WgradCall c = wgrad_call(y1_16, nullptr, 0, gy, workspace, N, H, W, Cin, Cout, stream);
+  c.gsc = gsc; c.x_f16 = true; c.aff = &a;
+  return wgrad_f16_run(c, gw);
 }
 // ... and the block's 1x1 shortcut weight gradient in the same pass: gw10 [10][Cin][Cout], rows 0..8 = the 3x3 taps, row 9 = the
 // shortcut's (as smsut_conv2d_wgrad_mfma_sc); gsc = smsut_absmax_scale2(gy, gs).
-int smsut_conv2d_wgrad_sc_f16_supported(int N, int H, int W, int Cin, int Cout) {
-  return smsut_conv2d_wgrad_f16_supported(N, H, W, Cin, Cout);
-}
+int smsut_conv2d_wgrad_sc_f16_supported(int N, int H, int W, int Cin, int Cout) { return wgrad_f16_shape_ok(N, H, W, Cin, Cout); }
 int64_t smsut_conv2d_wgrad_sc_f16_ws(int N, int H, int W, int Cin, int Cout) {
-  return (int64_t)plan_wgrad_f16(N, H, W, Cin, Cout).splits * 10 * Cin * Cout;
+  return (int64_t)plan_wgrad_f16(N, H, W, Cin, Cout, true).splits * 10 * Cin * Cout;
 }
 int smsut_conv2d_wgrad_sc_f16(const float* x, const float* x2, int ca, const float* gy, const float* gs, float* gw10,
                               float* workspace, const float* gsc, int N, int H, int W, int Cin, int Cout, void* stream) {
-  SMSUT_REQUIRE(x && gy && gs && gw10 && workspace && gsc && smsut_conv2d_wgrad_sc_f16_supported(N, H, W, Cin, Cout));
-  SMSUT_REQUIRE(!x2 || (ca > 0 && ca < Cin && ca % 16 == 0));
-  hipStream_t st = (hipStream_t)stream;
-  const WgradPlan p = plan_wgrad_f16(N, H, W, Cin, Cout);
-  launch_wgrad_f16(x, x2, ca, gy, gs, workspace, gsc, N, H, W, Cin, Cout, p, st);
-  launch_sum_splits(workspace, gw10, 10 * Cin * Cout, p.splits, st);
-  SMSUT_LAUNCH_CHECK();
-  return SMSUT_OK;
+  SMSUT_REQUIRE(gs && gsc);
+  WgradCall c = wgrad_call(x, x2, ca, gy, workspace, N, H, W, Cin, Cout, stream);
+  c.gs = gs; c.gsc = gsc;
+  return wgrad_f16_run(c, gw10);
 }
 
 int64_t smsut_absmax_scale_ws(int64_t n) { (void)n; return 1024; }
@@ -3551,18 +3530,11 @@ int64_t smsut_convT2x2_wgrad_mfma_ws(int N, int H, int W, int Cin, int Cout) {
 int smsut_convT2x2_wgrad_mfma(const float* x, const float* gy, float* gw, float* workspace, int N, int H, int W, int Cin,
                               int Cout, void* stream) {
   SMSUT_REQUIRE(x && gy && gw && workspace && N > 0 && H > 0 && W > 0 && smsut_convT2x2_mfma_supported(Cin, Cout));
-  hipStream_t st = (hipStream_t)stream;
-  const WgradPlan p = plan_wgrad(N, H, W, Cin, Cout);
-  int rc;
-  if (p.cit == 1 && p.cot == 1) rc = launch_wgrad<1, 1, 1>(x, gy, workspace, N, H, W, Cin, Cout, p, 2, 4, st);
-  else if (p.cit == 1) rc = launch_wgrad<1, 1, 2>(x, gy, workspace, N, H, W, Cin, Cout, p, 2, 4, st);
-  else if (p.cot == 1) rc = launch_wgrad<1, 2, 1>(x, gy, workspace, N, H, W, Cin, Cout, p, 2, 4, st);
-  else rc = launch_wgrad<1, 2, 2>(x, gy, workspace, N, H, W, Cin, Cout, p, 2, 4, st);
-  if (rc != 0) return SMSUT_EINVAL;
-  const int wsize = 4 * Cin * Cout;
-  launch_sum_splits(workspace, gw, wsize, p.splits, st);
-  SMSUT_LAUNCH_CHECK();
-  return SMSUT_OK;
+  WgradCall c = wgrad_call(x, nullptr, 0, gy, workspace, N, H, W, Cin, Cout, stream);
+  c.KS = 1;
+  WgradPlan p = plan_wgrad(N, H, W, Cin, Cout);
+  p.rows = 4;                                   // four taps, each a 1x1 weight gradient against its quarter of the 2x larger gy
+  return wgrad_reduce(launch_wgrad_rows(c, p, /*up=*/2), c, p, gw);
 }
 
 }  // extern "C"

@@ -55,7 +55,7 @@ struct RrArgs {
   int RC;                                       // rows per wave-unit (H % RC == 0, RC % R == 0)
   int groups_per_split;                         // groups of WS wave-units a workgroup walks
   int total_wu;                                 // N * (H / RC) * (W / 16)
-  RrAff aff;
+  AffRef aff;
   // PAIRED launch (smsut_conv2d_wgrad_pair): images n >= N1 belong to a SECOND set of tensors that went through the same conv
   // (another forward pass of the same layer) -- one launch, one slab set, both sets summed in the accumulators.  N1 == N: one set.
   int N1;
@@ -369,17 +369,18 @@ constexpr int RR_TARGET = 512;          // workgroups the split plan aims for: v
 constexpr int RR_TARGET4 = 256;         // ... and variant 4
 constexpr int RR_RCMAX = 64;            // longest row run of a work unit
 
-RrPlan plan_rr(int N, int H, int W, int Cin, int Cout, const float* x2, int ca, bool aff, bool sc) {
+RrPlan plan_rr(const WgradKey& k) {
+  const int N = k.N, H = k.H, W = k.W, Cin = k.Cin, Cout = k.Cout;
   RrPlan p{};
   if (N <= 0 || H < 4 || W < 16 || (W % 16) || (H % 4) || (Cin % 16) || (Cout % 16)) return p;
   if ((int64_t)H * W * (Cin > Cout ? Cin : Cout) >= (1ll << 29)) return p;       // byte offsets inside an image are 32-bit
-  if (x2 && (ca <= 0 || ca >= Cin || (ca % 16))) return p;
+  if (k.cat && Cin < 32) return p;                                                // no seam with ca % 16 == 0 inside 16 channels
   if (Cin == 16 && Cout == 16) { p.variant = 1; p.slab_ci = 16; p.slab_co = 16; p.ws = 4; }
   else if (Cin == 32 && Cout == 16) { p.variant = 2; p.slab_ci = 32; p.slab_co = 16; p.ws = 4; }
   else if (Cin == 16 && Cout == 32) { p.variant = 3; p.slab_ci = 16; p.slab_co = 32; p.ws = 4; }
   else if (Cin % 32 == 0 && Cout % 32 == 0) { p.variant = 4; p.slab_ci = 32; p.slab_co = 32; p.ws = 4; }
   else return p;
-  if (aff && x2) return RrPlan{};
+  if (k.aff && k.cat) return RrPlan{};
   p.R = (p.variant == 4 && !RR_V4R8) ? 4 : 8;
   if (H % p.R) {
     if (H % 4) return RrPlan{};
@@ -400,7 +401,7 @@ RrPlan plan_rr(int N, int H, int W, int Cin, int Cout, const float* x2, int ca, 
   const int groups = (p.total_wu + p.ws - 1) / p.ws;
   if (want > groups) want = groups;
   // keep the slabs sum_splits re-reads bounded (as plan_wgrad: 8 M floats)
-  const int64_t wsz = (int64_t)Cin * Cout * (sc ? 10 : 9);
+  const int64_t wsz = (int64_t)Cin * Cout * (k.sc ? 10 : 9);
   int cap = (int)(((int64_t)8 << 20) / wsz);
   if (cap < 1) cap = 1;
   if (want > cap) want = cap;
@@ -439,43 +440,42 @@ static unsigned long long* g_rr_dbg = nullptr;
 extern "C" void smsut_dbg_rr_stamps(unsigned long long* p) { g_rr_dbg = p; }
 #endif
 
-bool smsut_wgrad_rr_eligible(int N, int H, int W, int Cin, int Cout, const float* x2, int ca, bool aff, bool sc) {
-  return plan_rr(N, H, W, Cin, Cout, x2, ca, aff, sc).variant != 0;
-}
-int smsut_wgrad_rr_splits(int N, int H, int W, int Cin, int Cout, const float* x2, int ca, bool aff, bool sc) {
-  const RrPlan p = plan_rr(N, H, W, Cin, Cout, x2, ca, aff, sc);
+int smsut_wgrad_rr_splits(const WgradKey& k) {
+  const RrPlan p = plan_rr(k);
   return p.variant ? p.splits : 0;
 }
 
-int smsut_wgrad_rr_launch(const float* x, const float* x2, int ca, const float* gy, const float* gs, float* part, int N, int H,
-                          int W, int Cin, int Cout, const RrAff* aff, hipStream_t st, const RrSetB* b) {
-  const RrPlan p = plan_rr(N, H, W, Cin, Cout, x2, ca, aff != nullptr, gs != nullptr);
-  if (!p.variant) return -1;
-  if (b && (b->n <= 0 || b->n >= N || !b->x || !b->gy || (x2 != nullptr) != (b->x2 != nullptr) || (gs != nullptr) != (b->gs != nullptr) ||
-            (aff != nullptr) != (b->mean != nullptr && b->rstd != nullptr)))
+int smsut_wgrad_rr_launch(const WgradCall& c) {
+  const WgradKey k = c.key();
+  const RrPlan p = plan_rr(k);
+  if (!p.variant || c.KS != 3 || c.x_f16 || c.gsc) return -1;
+  if (c.x2 && (c.ca <= 0 || c.ca >= c.Cin || (c.ca % 16))) return -1;
+  const WgradSetB* b = c.b;
+  if (b && (b->n <= 0 || b->n >= c.N || !b->x || !b->gy || k.cat != (b->x2 != nullptr) || k.sc != (b->gs != nullptr) ||
+            k.aff != (b->mean != nullptr) || k.aff != (b->rstd != nullptr)))
     return -1;
   RrArgs a{};
-  a.x = x; a.x2 = x2; a.ca = ca; a.gy = gy; a.gs = gs; a.part = part;
-  a.N = N; a.H = H; a.W = W; a.Cin = Cin; a.Cout = Cout;
+  a.x = (const float*)c.x; a.x2 = c.x2; a.ca = c.ca; a.gy = c.gy; a.gs = c.gs; a.part = c.part;
+  a.N = c.N; a.H = c.H; a.W = c.W; a.Cin = c.Cin; a.Cout = c.Cout;
   a.RC = p.RC; a.groups_per_split = p.groups_per_split; a.total_wu = p.total_wu;
-  if (aff) a.aff = *aff;
-  a.N1 = N;
+  if (c.aff) a.aff = *c.aff;
+  a.N1 = c.N;
   if (b) {
-    a.N1 = N - b->n;
+    a.N1 = c.N - b->n;
     a.xB = b->x; a.x2B = b->x2; a.gyB = b->gy; a.gsB = b->gs; a.meanB = b->mean; a.rstdB = b->rstd;
   }
 #ifdef SMSUT_STAMPS
   a.dbg = g_rr_dbg;
 #endif
   switch (p.variant) {
-    case 1: return p.R == 8 ? launch_v<1, 1, 1, 1, 8, 3>(a, p, st) : launch_v<1, 1, 1, 1, 4, 1>(a, p, st);
-    case 2: return p.R == 8 ? launch_v<2, 1, 1, 1, 8, 3>(a, p, st) : launch_v<2, 1, 1, 1, 4, 1>(a, p, st);
-    case 3: return p.R == 8 ? launch_v<1, 2, 1, 1, 8, 3>(a, p, st) : launch_v<1, 2, 1, 1, 4, 1>(a, p, st);
+    case 1: return p.R == 8 ? launch_v<1, 1, 1, 1, 8, 3>(a, p, c.stream) : launch_v<1, 1, 1, 1, 4, 1>(a, p, c.stream);
+    case 2: return p.R == 8 ? launch_v<2, 1, 1, 1, 8, 3>(a, p, c.stream) : launch_v<2, 1, 1, 1, 4, 1>(a, p, c.stream);
+    case 3: return p.R == 8 ? launch_v<1, 2, 1, 1, 8, 3>(a, p, c.stream) : launch_v<1, 2, 1, 1, 4, 1>(a, p, c.stream);
 #if RR_V4R8
-    case 4: return p.R == 8 ? (gs ? launch_v<2, 2, 1, 1, 8, 2>(a, p, st) : launch_v<2, 2, 1, 1, 8, 3>(a, p, st))
-                            : launch_v<2, 2, 1, 1, 4, 1>(a, p, st);
+    case 4: return p.R == 8 ? (k.sc ? launch_v<2, 2, 1, 1, 8, 2>(a, p, c.stream) : launch_v<2, 2, 1, 1, 8, 3>(a, p, c.stream))
+                            : launch_v<2, 2, 1, 1, 4, 1>(a, p, c.stream);
 #else
-    case 4: return launch_v<2, 2, 1, 1, 4, 1>(a, p, st);
+    case 4: return launch_v<2, 2, 1, 1, 4, 1>(a, p, c.stream);
 #endif
   }
   return -1;
