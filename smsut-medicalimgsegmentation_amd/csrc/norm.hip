@@ -909,81 +909,289 @@ inline int slab_count(int N, int chunks, int C, int vec) {
   return z;
 }
 
+// ---- host side ---------------------------------------------------------------------------------------------------------------------
+// The geometry of a partial-sum launch (in_moments_partial, restail_bwd_partial): pixels per chunk, chunks per image, grid = (chunks,
+// N, channel slabs).  one_chunk: the kernel finalises by itself (fin_emit) and no in_moments_final launch follows.
+struct Reduce { int ppc, chunks; dim3 grid; bool one_chunk; };
+inline Reduce plan_reduce(int N, int HW, int C) {
+  Reduce r;
+  r.ppc = pick_chunk(HW, C, N);
+  r.chunks = (int)cdiv64(HW, r.ppc);
+  r.grid = dim3(r.chunks, N, slab_count(N, r.chunks, C, C % 4 == 0 ? 4 : 1));
+  r.one_chunk = r.chunks == 1;
+  return r;
+}
+// chunk partials -> the per-(n, c) means o (o.eps: MODE 0 only): 16 channels per workgroup
+template <int MODE>
+inline void launch_final(const float* part, int chunks, int N, int HW, int C, const FinOut& o, hipStream_t st) {
+  in_moments_final<MODE><<<dim3((C + 15) / 16, N), TPB, 0, st>>>(part, chunks, C, HW, o.eps, o.o0, o.o1, o.o2);
+}
+
+// The form of an instantiation as the launch sites name it (the F_* idiom of common.h): one bit per template parameter; the
+// *_kernel<F> aliases turn a mask into the kernel's own parameter list, whose spelling the trace summaries match.
+enum : unsigned {
+  N_VEC4 = 1u << 0,     // float4 channel groups (C % 4 == 0); without it one channel per lane
+  N_HS = 1u << 1,       // half storage: x | y2 and s are fp16
+  N_YH = 1u << 2,       // in_apply_fwd: y stored as fp16 too
+  N_AMAX = 1u << 3,     // max |result| per workgroup handed over (amax_emit)
+  N_POOLG = 1u << 4,    // gy is the gradient of the 2x2-average-pooled output
+  N_REMASK = 1u << 5,   // tail backward: activation mask recomputed from y2 and s, `out` not read
+  N_FIN = 1u << 6,      // restail_bwd_partial: means finalised inside the launch (tickets)
+  N_MPG = 1u << 7,      // tail backward: pooled path's gradient routed in while loading (MaxRef)
+  N_V4R = N_VEC4 | N_REMASK,
+};
+constexpr int form_vec(unsigned F) { return (F & N_VEC4) ? 4 : 1; }
+constexpr bool has(unsigned F, unsigned bit) { return (F & bit) != 0; }
+template <int MODE, unsigned F> constexpr auto moments_kernel = in_moments_partial<MODE, form_vec(F), has(F, N_POOLG)>;
+template <unsigned F> constexpr auto apply_fwd_kernel = in_apply_fwd<form_vec(F), has(F, N_HS), has(F, N_YH)>;
+template <unsigned F> constexpr auto apply_bwd_kernel = in_apply_bwd<form_vec(F), has(F, N_HS), has(F, N_AMAX), has(F, N_POOLG)>;
+template <unsigned F> constexpr auto tail_fwd_kernel = restail_fwd<form_vec(F), has(F, N_HS)>;
+template <unsigned F>
+constexpr auto tail_partial_kernel = restail_bwd_partial<form_vec(F), has(F, N_REMASK), has(F, N_HS), has(F, N_FIN), has(F, N_MPG)>;
+template <unsigned F>
+constexpr auto tail_apply_kernel = restail_bwd_apply<form_vec(F), has(F, N_REMASK), has(F, N_HS), has(F, N_AMAX), has(F, N_MPG)>;
+// go(Form<F>{}) for the F of the list that the run-time mask m equals: the list IS the set of instantiations of that kernel; -1
+// ("nothing launched") for a mask that is not in it
+template <unsigned... Fs, class Go>
+int go_form(unsigned m, Go&& go) {
+  int rc = SMSUT_EINVAL;
+  (void)((m == Fs ? (rc = go(Form<Fs>{}), true) : false) || ...);
+  return rc;
+}
+inline unsigned vec_form(int C) { return C % 4 == 0 ? N_VEC4 : 0u; }
+template <class Call>                  // NormCall | TailCall: the per-image walks index in 32 bits
+inline bool shape_ok(const Call& c) { return c.N > 0 && c.HW > 0 && c.C > 0 && (int64_t)c.HW * c.C < (1ll << 31); }
+
+// ---- one description of an InstanceNorm launch sequence: statistics (own reduction | the conv epilogue's partials) + apply ------------
+// x [N,HW,C] (fp16 with hs); gy: gradient of y (of the 2x2-average-pooled y, [N,H/2,W/2,C], with pool_w = the plane's width W);
+// backward with beta == null: no activation.  mean, rstd, a_mean (mean gz), b_mean (mean gz * xhat) [N,C] are what the apply kernels
+// read; `sums` is where the statistics step writes them first (with the forward's eps) -- from this call's own reduction through
+// `workspace`, or forward from the conv epilogue's `partials` [N][chunks][C][2].  y: forward result (fp16 with y_f16; pooled with
+// pool_w); gx, ggamma, gbeta (both or neither): backward results; amax: smsut_amax_blocks slots for max |gx|.
+struct NormCall {
+  const void* x = nullptr; const float* gy = nullptr; const float* gamma = nullptr; const float* beta = nullptr;
+  const float* mean = nullptr; const float* rstd = nullptr; const float* a_mean = nullptr; const float* b_mean = nullptr;
+  FinOut sums{};
+  void* y = nullptr; float* gx = nullptr; float* ggamma = nullptr; float* gbeta = nullptr; float* amax = nullptr;
+  float* workspace = nullptr; const float* partials = nullptr;
+  int chunks = 0, pool_w = 0, N = 0, HW = 0, C = 0, has_act = 1;
+  float slope = 0.f; bool hs = false, y_f16 = false; hipStream_t stream = nullptr;
+};
+inline NormCall norm_call(const void* x, const float* mean, const float* rstd, const float* gamma, const float* beta, int N, int HW,
+                          int C, void* stream) {
+  NormCall c;
+  c.x = x; c.mean = mean; c.rstd = rstd; c.gamma = gamma; c.beta = beta; c.N = N; c.HW = HW; c.C = C; c.stream = (hipStream_t)stream;
+  return c;
+}
+// which instantiations a NormCall runs: partial sums, forward apply, backward apply
+struct NormForms { unsigned moments, fwd, bwd; };
+inline NormForms norm_forms(const NormCall& c) {
+  const unsigned v = vec_form(c.C), hs = c.hs ? N_HS : 0u, pg = c.pool_w ? N_POOLG : 0u;
+  return NormForms{v | pg, v | hs | (c.y_f16 ? N_YH : 0u), v | hs | pg | (c.amax ? N_AMAX : 0u)};
+}
+
+// the per-(n, c) means of MODE's sums over (t0, t1, t2) -> c.sums: partial sums into c.workspace, then in_moments_final unless the
+// one-chunk partial kernel finalised by itself.  (MODE 0 has no statistics or affine parameters to read.)
+template <int MODE>
+int launch_moments(const NormCall& c, const float* t0, const float* t1, const float* t2) {
+  const Reduce r = plan_reduce(c.N, c.HW, c.C);
+  const FinOut fin = r.one_chunk ? c.sums : FinOut{};
+  auto go = [&](auto form) {
+    constexpr auto kern = moments_kernel<MODE, decltype(form)::value>;
+    kern<<<r.grid, TPB, 0, c.stream>>>(t0, t1, t2, MODE ? c.gamma : nullptr, MODE ? c.beta : nullptr, MODE ? c.mean : nullptr,
+                                       MODE ? c.rstd : nullptr, c.workspace, c.HW, c.C, r.ppc, c.slope, fin, c.pool_w);
+    return 0;
+  };
+  int rc;
+  if constexpr (MODE == 1) rc = go_form<0u, N_VEC4, N_POOLG, N_POOLG | N_VEC4>(norm_forms(c).moments, go);
+  else rc = go_form<0u, N_VEC4>(norm_forms(c).moments, go);
+  if (rc == 0 && !r.one_chunk) launch_final<MODE>(c.workspace, r.chunks, c.N, c.HW, c.C, c.sums, c.stream);
+  return rc;
+}
+
+// forward: statistics, then y = act(IN(x)) -- or its 2x2 average (pool_w)
+int run_in_fwd(const NormCall& c) {
+  SMSUT_REQUIRE(c.x && c.gamma && c.beta && c.y && c.mean && c.rstd && c.sums.o0 && c.sums.o1 && shape_ok(c) &&
+                (c.partials ? c.chunks > 0 : c.workspace != nullptr));
+  SMSUT_REQUIRE(c.hs ? c.C % 4 == 0 && !c.pool_w : !c.y_f16);      // the forms the apply kernels have
+  const float* x = (const float*)c.x;
+  if (c.partials) launch_final<0>(c.partials, c.chunks, c.N, c.HW, c.C, c.sums, c.stream);
+  else SMSUT_REQUIRE(launch_moments<0>(c, x, nullptr, nullptr) == 0);
+  const unsigned m = norm_forms(c).fwd;
+  const int V = form_vec(m);
+  if (c.pool_w) {
+    const int H = c.HW / c.pool_w, W = c.pool_w;
+    const dim3 g = img_grid((int64_t)(H / 2) * (W / 2) * (c.C / V), c.N);
+    if (V == 4) in_apply_pool_fwd<4><<<g, TPB, 0, c.stream>>>(x, c.mean, c.rstd, c.gamma, c.beta, (float*)c.y, H, W, c.C, c.slope);
+    else in_apply_pool_fwd<1><<<g, TPB, 0, c.stream>>>(x, c.mean, c.rstd, c.gamma, c.beta, (float*)c.y, H, W, c.C, c.slope);
+  } else {
+    auto go = [&](auto form) {
+      constexpr auto kern = apply_fwd_kernel<decltype(form)::value>;
+      kern<<<img_grid((int64_t)c.HW * (c.C / V), c.N), TPB, 0, c.stream>>>(x, c.mean, c.rstd, c.gamma, c.beta, (float*)c.y, c.HW, c.C,
+                                                                            c.slope, c.has_act);
+      return 0;
+    };
+    SMSUT_REQUIRE((go_form<0u, N_VEC4, N_VEC4 | N_HS, N_VEC4 | N_HS | N_YH>(m, go)) == 0);
+  }
+  SMSUT_LAUNCH_CHECK();
+  return SMSUT_OK;
+}
+
+// backward: a, b (with a workspace; else they are given), then gx and the affine gradients (block 0 of the apply kernel)
+int run_in_bwd(const NormCall& c) {
+  SMSUT_REQUIRE(c.gy && c.x && c.mean && c.rstd && c.gamma && c.gx && c.a_mean && c.b_mean && shape_ok(c));
+  SMSUT_REQUIRE((!c.hs || c.C % 4 == 0) && !(c.pool_w && (c.hs || c.amax)));      // the forms in_apply_bwd has
+  const float* x = (const float*)c.x;
+  if (c.workspace) SMSUT_REQUIRE(launch_moments<1>(c, c.gy, x, nullptr) == 0);
+  float* gg = (c.ggamma && c.gbeta) ? c.ggamma : nullptr;
+  const unsigned m = norm_forms(c).bwd;
+  auto go = [&](auto form) {
+    constexpr auto kern = apply_bwd_kernel<decltype(form)::value>;
+    kern<<<img_grid((int64_t)c.HW * (c.C / form_vec(m)), c.N), TPB, 0, c.stream>>>(c.gy, x, c.beta, c.mean, c.rstd, c.gamma, c.a_mean,
+                                                                                  c.b_mean, c.gx, c.HW, c.C, c.slope, c.N, gg, c.gbeta,
+                                                                                  c.amax, c.pool_w);
+    return 0;
+  };
+  SMSUT_REQUIRE((go_form<0u, N_VEC4, N_AMAX, N_VEC4 | N_AMAX, N_VEC4 | N_HS, N_VEC4 | N_HS | N_AMAX, N_POOLG, N_POOLG | N_VEC4>(m, go)) == 0);
+  SMSUT_LAUNCH_CHECK();
+  return SMSUT_OK;
+}
+
+// ---- one description of a residual-tail launch sequence, forward or backward ---------------------------------------------------------
+// t: y2, s (fp16 with hs), their statistics and affine parameters; ms == null: identity shortcut.
+// Forward: y = the result `out` [N,HW,C]; with `pooled` also its 2x2 pooling [N,H/2,W/2,C] in the same pass (W: the plane's width) --
+// MAX pooling with the positions of the maxima in idx, AVERAGE pooling with idx == null.
+// Backward: gout and the forward's `out` (not read when the mask is recomputed, N_REMASK) -> gy2, gs (gradients of the two raw conv
+// outputs), a / b2 / bs_mean ([N,C] scratch outputs), the affine gradients (ggs, gbs: conv shortcut); workspace: float[N * chunks * C
+// * 3].  Optional: amax (2 * smsut_amax_blocks slots: max |gy2|, max |gs|), tickets (in-launch finalize wanted; int [N], zero on entry
+// and exit), mr.gp (gout is the skip connection's gradient only, the pooled path's is routed in while loading).
+struct TailCall {
+  TailRef t{};
+  int N = 0, HW = 0, C = 0, W = 0;
+  float slope = 0.f; bool hs = false; hipStream_t stream = nullptr;
+  float* y = nullptr; float* pooled = nullptr; unsigned int* idx = nullptr;
+  const float* gout = nullptr; const float* out = nullptr;
+  float* gy2 = nullptr; float* gs = nullptr; float* a_mean = nullptr; float* b2_mean = nullptr; float* bs_mean = nullptr;
+  float* gg2 = nullptr; float* gb2 = nullptr; float* ggs = nullptr; float* gbs = nullptr; float* workspace = nullptr;
+  float* amax = nullptr; int* tickets = nullptr; MaxRef mr{nullptr, nullptr, 0};
+};
+inline TailCall tail_call(const TailRef& t, int N, int HW, int C, float slope, void* stream) {
+  TailCall c;
+  c.t = t; c.N = N; c.HW = HW; c.C = C; c.slope = slope; c.stream = (hipStream_t)stream;
+  return c;
+}
+
+// out = act(IN(y2) + (IN(s) | s)), with the 2x2 pooling of `out` in the same pass when c.pooled
+int run_tail_fwd(const TailCall& c) {
+  const TailRef& t = c.t;
+  SMSUT_REQUIRE(t.y2 && t.m2 && t.r2 && t.g2 && t.b2 && t.s && c.y && shape_ok(c) && (!t.ms || (t.rs && t.gs && t.bs)));
+  SMSUT_REQUIRE(!(c.hs || c.pooled) || c.C % 4 == 0);
+  if (c.pooled) {
+    const dim3 g = img_grid((int64_t)(c.HW / c.W / 2) * (c.W / 2) * (c.C / 4), c.N);
+    if (c.hs) restail_fwd_pool<true><<<g, TPB, 0, c.stream>>>(t, c.y, c.pooled, c.idx, c.HW / c.W, c.W, c.C, c.slope);
+    else restail_fwd_pool<false><<<g, TPB, 0, c.stream>>>(t, c.y, c.pooled, c.idx, c.HW / c.W, c.W, c.C, c.slope);
+  } else {
+    const unsigned m = vec_form(c.C) | (c.hs ? N_HS : 0u);
+    auto go = [&](auto form) {
+      constexpr auto kern = tail_fwd_kernel<decltype(form)::value>;
+      kern<<<img_grid((int64_t)c.HW * (c.C / form_vec(m)), c.N), TPB, 0, c.stream>>>(t, c.y, c.HW, c.C, c.slope);
+      return 0;
+    };
+    SMSUT_REQUIRE((go_form<0u, N_VEC4, N_VEC4 | N_HS>(m, go)) == 0);
+  }
+  SMSUT_LAUNCH_CHECK();
+  return SMSUT_OK;
+}
+
+// Which instantiations the tail's backward runs.  N_REMASK: two-IN tail with both betas given.  fin_in (N_FIN in `partial`):
+// in-launch finalize -- tickets given, several chunks per image, fp32, recomputed mask, whole float4 channel groups: the
+// last-arriving workgroup of an image combines its partials and there is no in_moments_final<2> launch.
+struct TailBwdForms { unsigned partial, apply; bool fin_in; };
+inline TailBwdForms tail_bwd_forms(const TailCall& c, bool one_chunk) {
+  const bool remask = c.t.ms && c.t.b2 && c.t.bs;
+  const unsigned base = vec_form(c.C) | (remask ? N_REMASK : 0u) | (c.hs ? N_HS : 0u) | (c.mr.gp ? N_MPG : 0u);
+  const bool fin_in = c.tickets && !one_chunk && !c.hs && (base & N_V4R) == N_V4R;
+  return TailBwdForms{base | (fin_in ? N_FIN : 0u), base | (c.amax ? N_AMAX : 0u), fin_in};
+}
+
+// the three sums per (n, c) -> a / b2 / bs_mean, then gy2, gs and the affine gradients (block 0 of the apply kernel; gbs = gb2)
+int run_tail_bwd(const TailCall& c) {
+  const TailRef& t = c.t;
+  SMSUT_REQUIRE(c.gout && c.out && t.y2 && t.m2 && t.r2 && t.g2 && t.s && c.gy2 && c.gs && c.a_mean && c.b2_mean && c.bs_mean &&
+                c.gg2 && c.gb2 && c.workspace && shape_ok(c) && (!t.ms || (t.rs && t.gs && c.ggs && c.gbs)));
+  const Reduce r = plan_reduce(c.N, c.HW, c.C);
+  const TailBwdForms f = tail_bwd_forms(c, r.one_chunk);
+  SMSUT_REQUIRE(!c.mr.gp || (c.mr.W > 0 && c.HW % c.mr.W == 0));
+  SMSUT_REQUIRE(!(c.mr.gp || c.hs) || (f.apply & N_V4R) == N_V4R);      // routed pooled gradient, half storage: two-IN tail, channel quads
+  const FinOut sums{c.a_mean, c.b2_mean, c.bs_mean, 0.f};
+  const FinOut fin = (r.one_chunk || f.fin_in) ? sums : FinOut{};
+  auto partial = [&](auto form) {
+    constexpr auto kern = tail_partial_kernel<decltype(form)::value>;
+    kern<<<r.grid, TPB, 0, c.stream>>>(c.gout, c.out, t, c.workspace, c.HW, c.C, r.ppc, c.slope, fin, f.fin_in ? c.tickets : nullptr, c.mr);
+    return 0;
+  };
+  SMSUT_REQUIRE((go_form<0u, N_VEC4, N_REMASK, N_V4R, N_V4R | N_HS, N_V4R | N_MPG, N_V4R | N_HS | N_MPG, N_V4R | N_FIN,
+                         N_V4R | N_FIN | N_MPG>(f.partial, partial)) == 0);
+  if (!r.one_chunk && !f.fin_in) launch_final<2>(c.workspace, r.chunks, c.N, c.HW, c.C, sums, c.stream);
+  auto apply = [&](auto form) {
+    constexpr auto kern = tail_apply_kernel<decltype(form)::value>;
+    kern<<<img_grid((int64_t)c.HW * (c.C / form_vec(f.apply)), c.N), TPB, 0, c.stream>>>(
+        c.gout, c.out, t, c.a_mean, c.b2_mean, c.bs_mean, c.gy2, c.gs, c.HW, c.C, c.slope, c.N, c.gg2, c.gb2, t.ms ? c.ggs : nullptr,
+        t.ms ? c.gbs : nullptr, c.amax, c.mr);
+    return 0;
+  };
+  SMSUT_REQUIRE((go_form<0u, N_VEC4, N_REMASK, N_V4R, N_AMAX, N_VEC4 | N_AMAX, N_REMASK | N_AMAX, N_V4R | N_AMAX, N_V4R | N_HS,
+                         N_V4R | N_HS | N_AMAX, N_V4R | N_MPG, N_V4R | N_MPG | N_AMAX, N_V4R | N_MPG | N_HS,
+                         N_V4R | N_MPG | N_HS | N_AMAX>(f.apply, apply)) == 0);
+  SMSUT_LAUNCH_CHECK();
+  return SMSUT_OK;
+}
+
 }  // namespace
 
 extern "C" {
 
-int smsut_in_chunks(int N, int HW, int C) { return (int)cdiv64(HW, pick_chunk(HW, C, N)); }
+int smsut_in_chunks(int N, int HW, int C) { return plan_reduce(N, HW, C).chunks; }
 // channel slabs (gridDim.z) of the partial-sum launches of this shape: lets the tests check which reduction regime a case lands in
-int smsut_in_slabs(int N, int HW, int C) {
-  return slab_count(N, smsut_in_chunks(N, HW, C), C, C % 4 == 0 ? 4 : 1);
-}
+int smsut_in_slabs(int N, int HW, int C) { return (int)plan_reduce(N, HW, C).grid.z; }
 
 // workspace: float[N * smsut_in_chunks * C * 3]
 int smsut_instnorm_fwd(const float* x, const float* gamma, const float* beta, float* y, float* mean, float* rstd,
                        float* workspace, int N, int HW, int C, float eps, float slope, int has_act, void* stream) {
-  SMSUT_REQUIRE(x && gamma && beta && y && mean && rstd && workspace && N > 0 && HW > 0 && C > 0);
-  SMSUT_REQUIRE((int64_t)HW * C < (1ll << 31));       // per-image walks index in 32 bits
-  hipStream_t st = (hipStream_t)stream;
-  const int ppc = pick_chunk(HW, C, N);
-  const int chunks = (int)cdiv64(HW, ppc);
-  dim3 g(chunks, N, slab_count(N, chunks, C, C % 4 == 0 ? 4 : 1));
-  const FinOut fin = chunks == 1 ? FinOut{mean, rstd, nullptr, eps} : FinOut{};
-  if (C % 4 == 0)
-    in_moments_partial<0, 4><<<g, TPB, 0, st>>>(x, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, workspace, HW, C, ppc, slope, fin);
-  else
-    in_moments_partial<0, 1><<<g, TPB, 0, st>>>(x, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, workspace, HW, C, ppc, slope, fin);
-  if (!fin.o0) in_moments_final<0><<<dim3((C + 15) / 16, N), TPB, 0, st>>>(workspace, chunks, C, HW, eps, mean, rstd, nullptr);
-  const int64_t total = (int64_t)N * HW * C;
-  if (C % 4 == 0)
-    in_apply_fwd<4><<<img_grid((int64_t)HW * (C / 4), N), TPB, 0, st>>>(x, mean, rstd, gamma, beta, y, HW, C, slope, has_act);
-  else
-    in_apply_fwd<1><<<img_grid((int64_t)HW * C, N), TPB, 0, st>>>(x, mean, rstd, gamma, beta, y, HW, C, slope, has_act);
-  SMSUT_LAUNCH_CHECK();
-  return SMSUT_OK;
+  SMSUT_REQUIRE(workspace);
+  NormCall c = norm_call(x, mean, rstd, gamma, beta, N, HW, C, stream);
+  c.sums = FinOut{mean, rstd, nullptr, eps}; c.y = y; c.workspace = workspace; c.slope = slope; c.has_act = has_act;
+  return run_in_fwd(c);
 }
 
 // Same as smsut_instnorm_fwd when the {sum, sum^2} partials [N][chunks][C][2] were already produced by the conv
 // epilogue (smsut_conv2d_fwd_mfma_stats): finalise + normalise/activate only.
-static int instnorm_fwd_partials_launch(const float* x, const float* gamma, const float* beta, float* y, float* mean,
-                                        float* rstd, const float* partials, int chunks, int N, int HW, int C, float eps,
-                                        float slope, int has_act, void* stream, int hs) {
-  SMSUT_REQUIRE(x && gamma && beta && y && mean && rstd && partials && chunks > 0 && N > 0 && HW > 0 && C > 0);
-  SMSUT_REQUIRE((int64_t)HW * C < (1ll << 31));       // per-image walks index in 32 bits
-  hipStream_t st = (hipStream_t)stream;
-  in_moments_final<0><<<dim3((C + 15) / 16, N), TPB, 0, st>>>(partials, chunks, C, HW, eps, mean, rstd, nullptr);
-  const int64_t total = (int64_t)N * HW * C;
-  if (hs == 2)
-    in_apply_fwd<4, true, true><<<img_grid((int64_t)HW * (C / 4), N), TPB, 0, st>>>(x, mean, rstd, gamma, beta, y, HW, C, slope, has_act);
-  else if (hs)
-    in_apply_fwd<4, true><<<img_grid((int64_t)HW * (C / 4), N), TPB, 0, st>>>(x, mean, rstd, gamma, beta, y, HW, C, slope, has_act);
-  else if (C % 4 == 0)
-    in_apply_fwd<4><<<img_grid((int64_t)HW * (C / 4), N), TPB, 0, st>>>(x, mean, rstd, gamma, beta, y, HW, C, slope, has_act);
-  else
-    in_apply_fwd<1><<<img_grid((int64_t)HW * C, N), TPB, 0, st>>>(x, mean, rstd, gamma, beta, y, HW, C, slope, has_act);
-  SMSUT_LAUNCH_CHECK();
-  return SMSUT_OK;
-}
 int smsut_instnorm_fwd_partials(const float* x, const float* gamma, const float* beta, float* y, float* mean,
                                 float* rstd, const float* partials, int chunks, int N, int HW, int C, float eps,
                                 float slope, int has_act, void* stream) {
-  return instnorm_fwd_partials_launch(x, gamma, beta, y, mean, rstd, partials, chunks, N, HW, C, eps, slope, has_act, stream, 0);
+  SMSUT_REQUIRE(partials);
+  NormCall c = norm_call(x, mean, rstd, gamma, beta, N, HW, C, stream);
+  c.sums = FinOut{mean, rstd, nullptr, eps}; c.y = y; c.partials = partials; c.chunks = chunks; c.slope = slope; c.has_act = has_act;
+  return run_in_fwd(c);
 }
 // "half storage" (config 5): x is fp16 [N,HW,C] (the raw conv output a conv epilogue stored), y stays fp32; C % 4 == 0
 int smsut_instnorm_fwd_partials_hs(const void* x16, const float* gamma, const float* beta, float* y, float* mean,
                                    float* rstd, const float* partials, int chunks, int N, int HW, int C, float eps,
                                    float slope, int has_act, void* stream) {
-  SMSUT_REQUIRE(C % 4 == 0);
-  return instnorm_fwd_partials_launch((const float*)x16, gamma, beta, y, mean, rstd, partials, chunks, N, HW, C, eps, slope, has_act,
-                                      stream, 1);
+  SMSUT_REQUIRE(partials && C % 4 == 0);
+  NormCall c = norm_call(x16, mean, rstd, gamma, beta, N, HW, C, stream);
+  c.sums = FinOut{mean, rstd, nullptr, eps}; c.y = y; c.partials = partials; c.chunks = chunks; c.slope = slope; c.has_act = has_act; c.hs = true;
+  return run_in_fwd(c);
 }
 // ... and y stored as fp16 too (read by smsut_conv2d_fwd_mfma_stats_f16_hsx / smsut_conv2d_wgrad_f16_xh, which round to fp16 anyway)
 int smsut_instnorm_fwd_partials_hs2(const void* x16, const float* gamma, const float* beta, void* y16, float* mean,
                                     float* rstd, const float* partials, int chunks, int N, int HW, int C, float eps,
                                     float slope, int has_act, void* stream) {
-  SMSUT_REQUIRE(C % 4 == 0);
-  return instnorm_fwd_partials_launch((const float*)x16, gamma, beta, (float*)y16, mean, rstd, partials, chunks, N, HW, C, eps, slope,
-                                      has_act, stream, 2);
+  SMSUT_REQUIRE(partials && C % 4 == 0);
+  NormCall c = norm_call(x16, mean, rstd, gamma, beta, N, HW, C, stream);
+  c.sums = FinOut{mean, rstd, nullptr, eps}; c.y = y16; c.partials = partials; c.chunks = chunks; c.slope = slope; c.has_act = has_act;
+  c.hs = c.y_f16 = true;
+  return run_in_fwd(c);
 }
 
 // beta == null: no activation; otherwise the LeakyReLU mask is recomputed from x (sign of the normalised
@@ -991,28 +1199,11 @@ int smsut_instnorm_fwd_partials_hs2(const void* x16, const float* gamma, const f
 int smsut_instnorm_bwd(const float* gy, const float* x, const float* beta, const float* mean, const float* rstd,
                        const float* gamma, float* gx, float* a_mean, float* b_mean, float* ggamma, float* gbeta,
                        float* workspace, int N, int HW, int C, float slope, void* stream) {
-  SMSUT_REQUIRE(gy && x && mean && rstd && gamma && gx && a_mean && b_mean && workspace && N > 0 && HW > 0 && C > 0);
-  SMSUT_REQUIRE((int64_t)HW * C < (1ll << 31));       // per-image walks index in 32 bits
-  hipStream_t st = (hipStream_t)stream;
-  const int ppc = pick_chunk(HW, C, N);
-  const int chunks = (int)cdiv64(HW, ppc);
-  dim3 g(chunks, N, slab_count(N, chunks, C, C % 4 == 0 ? 4 : 1));
-  const FinOut fin = chunks == 1 ? FinOut{a_mean, b_mean, nullptr, 0.f} : FinOut{};
-  if (C % 4 == 0)
-    in_moments_partial<1, 4><<<g, TPB, 0, st>>>(gy, x, nullptr, gamma, beta, mean, rstd, workspace, HW, C, ppc, slope, fin);
-  else
-    in_moments_partial<1, 1><<<g, TPB, 0, st>>>(gy, x, nullptr, gamma, beta, mean, rstd, workspace, HW, C, ppc, slope, fin);
-  if (!fin.o0) in_moments_final<1><<<dim3((C + 15) / 16, N), TPB, 0, st>>>(workspace, chunks, C, HW, 0.f, a_mean, b_mean, nullptr);
-  float* gg = (ggamma && gbeta) ? ggamma : nullptr;       // affine gradients: computed by block 0 of the apply kernel
-  const int64_t total = (int64_t)N * HW * C;
-  if (C % 4 == 0)
-    in_apply_bwd<4><<<img_grid((int64_t)HW * (C / 4), N), TPB, 0, st>>>(gy, x, beta, mean, rstd, gamma, a_mean, b_mean, gx, HW, C, slope,
-                                                        N, gg, gbeta);
-  else
-    in_apply_bwd<1><<<img_grid((int64_t)HW * C, N), TPB, 0, st>>>(gy, x, beta, mean, rstd, gamma, a_mean, b_mean, gx, HW, C, slope,
-                                                    N, gg, gbeta);
-  SMSUT_LAUNCH_CHECK();
-  return SMSUT_OK;
+  SMSUT_REQUIRE(workspace);
+  NormCall c = norm_call(x, mean, rstd, gamma, beta, N, HW, C, stream);
+  c.gy = gy; c.gx = gx; c.a_mean = a_mean; c.b_mean = b_mean; c.sums = FinOut{a_mean, b_mean, nullptr, 0.f};
+  c.ggamma = ggamma; c.gbeta = gbeta; c.workspace = workspace; c.slope = slope;
+  return run_in_bwd(c);
 }
 
 // InstanceNorm + LeakyReLU + AvgPool2d(2) as one op (r05; bn1 -> relu -> avgpool of a stride-2 BottleBlock, reference
@@ -1021,15 +1212,10 @@ int smsut_instnorm_bwd(const float* gy, const float* x, const float* beta, const
 int smsut_instnorm_pool_fwd_partials(const float* x, const float* gamma, const float* beta, float* y, float* mean, float* rstd,
                                      const float* partials, int chunks, int N, int H, int W, int C, float eps, float slope,
                                      void* stream) {
-  SMSUT_REQUIRE(x && gamma && beta && y && mean && rstd && partials && chunks > 0 && N > 0 && H > 0 && W > 0 && C > 0 && !(H & 1) &&
-                !(W & 1) && (int64_t)H * W * C < (1ll << 31));
-  hipStream_t st = (hipStream_t)stream;
-  in_moments_final<0><<<dim3((C + 15) / 16, N), TPB, 0, st>>>(partials, chunks, C, H * W, eps, mean, rstd, nullptr);
-  const int64_t units = (int64_t)(H / 2) * (W / 2);
-  if (C % 4 == 0) in_apply_pool_fwd<4><<<img_grid(units * (C / 4), N), TPB, 0, st>>>(x, mean, rstd, gamma, beta, y, H, W, C, slope);
-  else in_apply_pool_fwd<1><<<img_grid(units * C, N), TPB, 0, st>>>(x, mean, rstd, gamma, beta, y, H, W, C, slope);
-  SMSUT_LAUNCH_CHECK();
-  return SMSUT_OK;
+  SMSUT_REQUIRE(partials && H > 0 && W > 0 && C > 0 && !(H & 1) && !(W & 1) && (int64_t)H * W * C < (1ll << 31));
+  NormCall c = norm_call(x, mean, rstd, gamma, beta, N, H * W, C, stream);
+  c.sums = FinOut{mean, rstd, nullptr, eps}; c.y = y; c.partials = partials; c.chunks = chunks; c.slope = slope; c.pool_w = W;
+  return run_in_fwd(c);
 }
 // ... its backward: gyp [N,H/2,W/2,C] is the gradient of the POOLED output; everything else as smsut_instnorm_bwd (beta non-null:
 // the mask is recomputed from x).  The full-resolution gradient 0.25 * gyp[h/2][w/2] is formed while loading, in both passes --
@@ -1037,28 +1223,11 @@ int smsut_instnorm_pool_fwd_partials(const float* x, const float* gamma, const f
 int smsut_instnorm_pool_bwd(const float* gyp, const float* x, const float* beta, const float* mean, const float* rstd,
                             const float* gamma, float* gx, float* a_mean, float* b_mean, float* ggamma, float* gbeta,
                             float* workspace, int N, int H, int W, int C, float slope, void* stream) {
-  SMSUT_REQUIRE(gyp && x && beta && mean && rstd && gamma && gx && a_mean && b_mean && workspace && N > 0 && H > 0 && W > 0 && C > 0 &&
-                !(H & 1) && !(W & 1) && (int64_t)H * W * C < (1ll << 31));
-  hipStream_t st = (hipStream_t)stream;
-  const int HW = H * W;
-  const int ppc = pick_chunk(HW, C, N);
-  const int chunks = (int)cdiv64(HW, ppc);
-  dim3 g(chunks, N, slab_count(N, chunks, C, C % 4 == 0 ? 4 : 1));
-  const FinOut fin = chunks == 1 ? FinOut{a_mean, b_mean, nullptr, 0.f} : FinOut{};
-  if (C % 4 == 0)
-    in_moments_partial<1, 4, true><<<g, TPB, 0, st>>>(gyp, x, nullptr, gamma, beta, mean, rstd, workspace, HW, C, ppc, slope, fin, W);
-  else
-    in_moments_partial<1, 1, true><<<g, TPB, 0, st>>>(gyp, x, nullptr, gamma, beta, mean, rstd, workspace, HW, C, ppc, slope, fin, W);
-  if (!fin.o0) in_moments_final<1><<<dim3((C + 15) / 16, N), TPB, 0, st>>>(workspace, chunks, C, HW, 0.f, a_mean, b_mean, nullptr);
-  float* gg = (ggamma && gbeta) ? ggamma : nullptr;
-  if (C % 4 == 0)
-    in_apply_bwd<4, false, false, true><<<img_grid((int64_t)HW * (C / 4), N), TPB, 0, st>>>(gyp, x, beta, mean, rstd, gamma, a_mean, b_mean,
-                                                                                         gx, HW, C, slope, N, gg, gbeta, nullptr, W);
-  else
-    in_apply_bwd<1, false, false, true><<<img_grid((int64_t)HW * C, N), TPB, 0, st>>>(gyp, x, beta, mean, rstd, gamma, a_mean, b_mean, gx,
-                                                                                   HW, C, slope, N, gg, gbeta, nullptr, W);
-  SMSUT_LAUNCH_CHECK();
-  return SMSUT_OK;
+  SMSUT_REQUIRE(beta && workspace && H > 0 && W > 0 && C > 0 && !(H & 1) && !(W & 1) && (int64_t)H * W * C < (1ll << 31));
+  NormCall c = norm_call(x, mean, rstd, gamma, beta, N, H * W, C, stream);
+  c.gy = gyp; c.gx = gx; c.a_mean = a_mean; c.b_mean = b_mean; c.sums = FinOut{a_mean, b_mean, nullptr, 0.f};
+  c.ggamma = ggamma; c.gbeta = gbeta; c.workspace = workspace; c.slope = slope; c.pool_w = W;
+  return run_in_bwd(c);
 }
 
 // Backward of smsut_instnorm_bwd (WGAN-GP double backward).  v = d/dgx; ug/ub = d/dggamma, d/dgbeta (may be null).
@@ -1067,28 +1236,20 @@ int smsut_instnorm_bwd2(const float* v, const float* ug, const float* ub, const 
                         const float* beta, const float* mean, const float* rstd, const float* gamma,
                         const float* a_mean, const float* b_mean, float* d_gy, float* d_x, float* d_gamma,
                         float* workspace, float* scratch, int N, int HW, int C, float slope, void* stream) {
-  SMSUT_REQUIRE(v && gy && x && mean && rstd && gamma && a_mean && b_mean && d_gy && d_x && d_gamma && workspace &&
-                scratch && N > 0 && HW > 0 && C > 0);
-  SMSUT_REQUIRE((int64_t)HW * C < (1ll << 31));       // per-image walks index in 32 bits
-  hipStream_t st = (hipStream_t)stream;
-  const int ppc = pick_chunk(HW, C, N);
-  const int chunks = (int)cdiv64(HW, ppc);
-  dim3 g(chunks, N, slab_count(N, chunks, C, C % 4 == 0 ? 4 : 1));
+  SMSUT_REQUIRE(v && gy && x && mean && rstd && gamma && a_mean && b_mean && d_gy && d_x && d_gamma && workspace && scratch);
   float* cvm = scratch; float* dvm = scratch + (size_t)N * C; float* em = scratch + 2 * (size_t)N * C;
-  const FinOut fin = chunks == 1 ? FinOut{cvm, dvm, em, 0.f} : FinOut{};
-  if (C % 4 == 0)
-    in_moments_partial<2, 4><<<g, TPB, 0, st>>>(v, x, gy, gamma, beta, mean, rstd, workspace, HW, C, ppc, slope, fin);
-  else
-    in_moments_partial<2, 1><<<g, TPB, 0, st>>>(v, x, gy, gamma, beta, mean, rstd, workspace, HW, C, ppc, slope, fin);
-  if (!fin.o0) in_moments_final<2><<<dim3((C + 15) / 16, N), TPB, 0, st>>>(workspace, chunks, C, HW, 0.f, cvm, dvm, em);
-  in_bwd2_gamma<<<(C + 63) / 64, 64, 0, st>>>(rstd, a_mean, b_mean, cvm, dvm, em, N, C, HW, d_gamma);
+  NormCall c = norm_call(x, mean, rstd, gamma, beta, N, HW, C, stream);
+  c.sums = FinOut{cvm, dvm, em, 0.f}; c.workspace = workspace; c.slope = slope;
+  SMSUT_REQUIRE(shape_ok(c));
+  launch_moments<2>(c, v, x, gy);
+  in_bwd2_gamma<<<(C + 63) / 64, 64, 0, c.stream>>>(rstd, a_mean, b_mean, cvm, dvm, em, N, C, HW, d_gamma);
   const int64_t total = (int64_t)N * HW * C;
   if (C % 4 == 0)
-    in_apply_bwd2<4><<<ew_grid(total / 4), TPB, 0, st>>>(v, x, gy, beta, mean, rstd, gamma, a_mean, b_mean, cvm, dvm, em,
-                                                          ug, ub, d_gy, d_x, total / 4, HW, C, slope);
+    in_apply_bwd2<4><<<ew_grid(total / 4), TPB, 0, c.stream>>>(v, x, gy, beta, mean, rstd, gamma, a_mean, b_mean, cvm, dvm, em,
+                                                                ug, ub, d_gy, d_x, total / 4, HW, C, slope);
   else
-    in_apply_bwd2<1><<<ew_grid(total), TPB, 0, st>>>(v, x, gy, beta, mean, rstd, gamma, a_mean, b_mean, cvm, dvm, em,
-                                                      ug, ub, d_gy, d_x, total, HW, C, slope);
+    in_apply_bwd2<1><<<ew_grid(total), TPB, 0, c.stream>>>(v, x, gy, beta, mean, rstd, gamma, a_mean, b_mean, cvm, dvm, em,
+                                                            ug, ub, d_gy, d_x, total, HW, C, slope);
   SMSUT_LAUNCH_CHECK();
   return SMSUT_OK;
 }
@@ -1097,7 +1258,7 @@ int smsut_instnorm_bwd2(const float* v, const float* ug, const float* ub, const 
 int smsut_in_finalize_fwd(const float* partials, int chunks, float* mean, float* rstd, int N, int HW, int C, float eps,
                           void* stream) {
   SMSUT_REQUIRE(partials && mean && rstd && chunks > 0 && N > 0 && HW > 0 && C > 0);
-  in_moments_final<0><<<dim3((C + 15) / 16, N), TPB, 0, (hipStream_t)stream>>>(partials, chunks, C, HW, eps, mean, rstd, nullptr);
+  launch_final<0>(partials, chunks, N, HW, C, FinOut{mean, rstd, nullptr, eps}, (hipStream_t)stream);
   SMSUT_LAUNCH_CHECK();
   return SMSUT_OK;
 }
@@ -1117,35 +1278,19 @@ int smsut_in_finalize_fwd2(const float* pa, int chunks_a, float* mean_a, float* 
 int smsut_in_finalize_bwd(const float* partials, int chunks, float* a_mean, float* b_mean, int N, int HW, int C,
                           void* stream) {
   SMSUT_REQUIRE(partials && a_mean && b_mean && chunks > 0 && N > 0 && HW > 0 && C > 0);
-  in_moments_final<1><<<dim3((C + 15) / 16, N), TPB, 0, (hipStream_t)stream>>>(partials, chunks, C, HW, 0.f, a_mean, b_mean, nullptr);
+  launch_final<1>(partials, chunks, N, HW, C, FinOut{a_mean, b_mean, nullptr, 0.f}, (hipStream_t)stream);
   SMSUT_LAUNCH_CHECK();
   return SMSUT_OK;
 }
 
 // gx = gamma*rstd*(gz - a - xhat*b) with gz ALREADY masked (output of smsut_conv2d_dgrad_mfma_bwdstats); ggamma / gbeta
 // (nullable) are the affine gradients sum_n HW*b, sum_n HW*a.
-static int in_apply_bwd_launch(const float* gz, const float* x, const float* mean, const float* rstd, const float* gamma,
-                               const float* a_mean, const float* b_mean, float* gx, float* ggamma, float* gbeta, float* amax, int N,
-                               int HW, int C, void* stream, bool hs = false) {
-  SMSUT_REQUIRE(gz && x && mean && rstd && gamma && a_mean && b_mean && gx && N > 0 && HW > 0 && C > 0);
-  hipStream_t st = (hipStream_t)stream;
-  float* gg = (ggamma && gbeta) ? ggamma : nullptr;
-  const int64_t total = (int64_t)N * HW * C;
-  SMSUT_REQUIRE((int64_t)HW * C < (1ll << 31));       // per-image walks index in 32 bits
-#define IN_APPLY_BWD(V, HSF, AM)                                                                                           \
-  in_apply_bwd<V, HSF, AM><<<img_grid((int64_t)HW * (C / V), N), TPB, 0, st>>>(gz, x, nullptr, mean, rstd, gamma, a_mean, b_mean, gx, \
-                                                                               HW, C, 0.f, N, gg, gbeta, amax)
-  if (hs) { if (amax) IN_APPLY_BWD(4, true, true); else IN_APPLY_BWD(4, true, false); }
-  else if (C % 4 == 0) { if (amax) IN_APPLY_BWD(4, false, true); else IN_APPLY_BWD(4, false, false); }
-  else { if (amax) IN_APPLY_BWD(1, false, true); else IN_APPLY_BWD(1, false, false); }
-#undef IN_APPLY_BWD
-  SMSUT_LAUNCH_CHECK();
-  return SMSUT_OK;
-}
 int smsut_in_apply_bwd(const float* gz, const float* x, const float* mean, const float* rstd, const float* gamma,
                        const float* a_mean, const float* b_mean, float* gx, float* ggamma, float* gbeta, int N, int HW, int C,
                        void* stream) {
-  return in_apply_bwd_launch(gz, x, mean, rstd, gamma, a_mean, b_mean, gx, ggamma, gbeta, nullptr, N, HW, C, stream);
+  NormCall c = norm_call(x, mean, rstd, gamma, nullptr, N, HW, C, stream);
+  c.gy = gz; c.a_mean = a_mean; c.b_mean = b_mean; c.gx = gx; c.ggamma = ggamma; c.gbeta = gbeta;
+  return run_in_bwd(c);
 }
 // workgroups of the per-image apply kernels (= amax slots per output tensor of the _amax entry points)
 int smsut_amax_blocks(int N, int HW, int C) {
@@ -1158,109 +1303,36 @@ int smsut_in_apply_bwd_amax(const float* gz, const float* x, const float* mean, 
                             const float* a_mean, const float* b_mean, float* gx, float* ggamma, float* gbeta, float* amax, int N,
                             int HW, int C, void* stream) {
   SMSUT_REQUIRE(amax);
-  return in_apply_bwd_launch(gz, x, mean, rstd, gamma, a_mean, b_mean, gx, ggamma, gbeta, amax, N, HW, C, stream);
+  NormCall c = norm_call(x, mean, rstd, gamma, nullptr, N, HW, C, stream);
+  c.gy = gz; c.a_mean = a_mean; c.b_mean = b_mean; c.gx = gx; c.ggamma = ggamma; c.gbeta = gbeta; c.amax = amax;
+  return run_in_bwd(c);
 }
 // "half storage" (config 5): x is fp16 [N,HW,C]; amax nullable; C % 4 == 0
 int smsut_in_apply_bwd_hs(const float* gz, const void* x16, const float* mean, const float* rstd, const float* gamma,
                           const float* a_mean, const float* b_mean, float* gx, float* ggamma, float* gbeta, float* amax, int N,
                           int HW, int C, void* stream) {
   SMSUT_REQUIRE(C % 4 == 0);
-  return in_apply_bwd_launch(gz, (const float*)x16, mean, rstd, gamma, a_mean, b_mean, gx, ggamma, gbeta, amax, N, HW, C, stream, true);
+  NormCall c = norm_call(x16, mean, rstd, gamma, nullptr, N, HW, C, stream);
+  c.gy = gz; c.a_mean = a_mean; c.b_mean = b_mean; c.gx = gx; c.ggamma = ggamma; c.gbeta = gbeta; c.amax = amax; c.hs = true;
+  return run_in_bwd(c);
 }
 
 // out = act(IN(y2) + (IN(s) | s)); ms == null: s is added as it is (identity shortcut).
-static int restail_fwd_launch(const float* y2, const float* m2, const float* r2, const float* g2, const float* b2, const float* s,
-                              const float* ms, const float* rs, const float* gs, const float* bs, float* out, bool hs, int N, int HW,
-                              int C, float slope, void* stream) {
-  SMSUT_REQUIRE(y2 && m2 && r2 && g2 && b2 && s && out && N > 0 && HW > 0 && C > 0 && (!ms || (rs && gs && bs)));
-  TailRef t{y2, m2, r2, g2, b2, s, ms, rs, gs, bs};
-  const int64_t total = (int64_t)N * HW * C;
-  SMSUT_REQUIRE((int64_t)HW * C < (1ll << 31));       // per-image walks index in 32 bits
-  hipStream_t st = (hipStream_t)stream;
-  if (hs) restail_fwd<4, true><<<img_grid((int64_t)HW * (C / 4), N), TPB, 0, st>>>(t, out, HW, C, slope);
-  else if (C % 4 == 0) restail_fwd<4><<<img_grid((int64_t)HW * (C / 4), N), TPB, 0, st>>>(t, out, HW, C, slope);
-  else restail_fwd<1><<<img_grid((int64_t)HW * C, N), TPB, 0, st>>>(t, out, HW, C, slope);
-  SMSUT_LAUNCH_CHECK();
-  return SMSUT_OK;
-}
 int smsut_restail_fwd(const float* y2, const float* m2, const float* r2, const float* g2, const float* b2, const float* s,
                       const float* ms, const float* rs, const float* gs, const float* bs, float* out, int N, int HW, int C,
                       float slope, void* stream) {
-  return restail_fwd_launch(y2, m2, r2, g2, b2, s, ms, rs, gs, bs, out, false, N, HW, C, slope, stream);
+  TailCall c = tail_call(TailRef{y2, m2, r2, g2, b2, s, ms, rs, gs, bs}, N, HW, C, slope, stream);
+  c.y = out;
+  return run_tail_fwd(c);
 }
 // "half storage" (config 5): y2 and s are fp16 [N,HW,C] (conv shortcut: ms != null), C % 4 == 0; everything else as above
 int smsut_restail_fwd_hs(const void* y2, const float* m2, const float* r2, const float* g2, const float* b2, const void* s,
                          const float* ms, const float* rs, const float* gs, const float* bs, float* out, int N, int HW, int C,
                          float slope, void* stream) {
   SMSUT_REQUIRE(ms && C % 4 == 0);
-  return restail_fwd_launch((const float*)y2, m2, r2, g2, b2, (const float*)s, ms, rs, gs, bs, out, true, N, HW, C, slope, stream);
-}
-
-// Backward of the tail.  workspace: float[N * smsut_in_chunks(N,HW,C) * C * 3]; a/b2/bs: [N,C] scratch outputs;
-// b2 / bs (the two IN betas, nullable): with ms and both betas the activation mask is recomputed from y2 and s and `out`
-// is not read (8 tensor passes instead of 10); otherwise the mask is the sign of `out`.
-// gy2, gs: gradients w.r.t. the two raw conv outputs (gs = gradient of the identity when ms == null);
-// gg2/gb2/ggs/gbs: affine gradients (ggs/gbs nullable when ms == null).
-static int restail_bwd_launch(const float* gout, const float* out, const float* y2, const float* m2, const float* r2,
-                              const float* g2, const float* b2, const float* s, const float* ms, const float* rs,
-                              const float* gs_, const float* bs, float* gy2, float* gs, float* a_mean, float* b2_mean, float* bs_mean, float* gg2, float* gb2, float* ggs,
-                              float* gbs, float* workspace, float* amax, int N, int HW, int C, float slope, void* stream,
-                              bool hs = false, int* tickets = nullptr, const MaxRef* mr = nullptr) {
-  SMSUT_REQUIRE(gout && out && y2 && m2 && r2 && g2 && s && gy2 && gs && a_mean && b2_mean && bs_mean && gg2 && gb2 &&
-                workspace && N > 0 && HW > 0 && C > 0 && (!ms || (rs && gs_ && ggs && gbs)));
-  // mr (r05): gout is the skip connection's gradient, the pooled path's is routed in while loading (two-IN tail, channel quads)
-  SMSUT_REQUIRE(!mr || (mr->gp && mr->W > 0 && HW % mr->W == 0 && ms && b2 && bs && C % 4 == 0));
-  SMSUT_REQUIRE((int64_t)HW * C < (1ll << 31));       // per-image walks index in 32 bits
-  const MaxRef mrv = mr ? *mr : MaxRef{nullptr, nullptr, 0};
-  TailRef t{y2, m2, r2, g2, b2, s, ms, rs, gs_, bs};
-  hipStream_t st = (hipStream_t)stream;
-  const int ppc = pick_chunk(HW, C, N);
-  const int chunks = (int)cdiv64(HW, ppc);
-  dim3 g(chunks, N, slab_count(N, chunks, C, C % 4 == 0 ? 4 : 1));
-  const bool remask = ms && b2 && bs;
-  const FinOut fin = chunks == 1 ? FinOut{a_mean, b2_mean, bs_mean, 0.f} : FinOut{};
-#define TAIL_PARTIAL(V, R) restail_bwd_partial<V, R><<<g, TPB, 0, st>>>(gout, out, t, workspace, HW, C, ppc, slope, fin)
-  // in-launch finalize (several chunks per image, fp32, the two-IN tail on whole float4 channel groups): the last-arriving
-  // workgroup of an image combines its partials -- no in_moments_final<2> launch
-  const bool fin_in = tickets && !fin.o0 && !hs && remask && C % 4 == 0;
-  if (fin_in && mr) {
-    restail_bwd_partial<4, true, false, true, true><<<g, TPB, 0, st>>>(gout, out, t, workspace, HW, C, ppc, slope,
-                                                                       FinOut{a_mean, b2_mean, bs_mean, 0.f}, tickets, mrv);
-  } else if (fin_in) {
-    restail_bwd_partial<4, true, false, true><<<g, TPB, 0, st>>>(gout, out, t, workspace, HW, C, ppc, slope,
-                                                                 FinOut{a_mean, b2_mean, bs_mean, 0.f}, tickets);
-  } else if (hs) {
-    SMSUT_REQUIRE(remask && C % 4 == 0);
-    if (mr) restail_bwd_partial<4, true, true, false, true><<<g, TPB, 0, st>>>(gout, out, t, workspace, HW, C, ppc, slope, fin, nullptr, mrv);
-    else restail_bwd_partial<4, true, true><<<g, TPB, 0, st>>>(gout, out, t, workspace, HW, C, ppc, slope, fin);
-  } else if (mr) {
-    restail_bwd_partial<4, true, false, false, true><<<g, TPB, 0, st>>>(gout, out, t, workspace, HW, C, ppc, slope, fin, nullptr, mrv);
-  } else if (C % 4 == 0) { if (remask) TAIL_PARTIAL(4, true); else TAIL_PARTIAL(4, false); }
-  else { if (remask) TAIL_PARTIAL(1, true); else TAIL_PARTIAL(1, false); }
-#undef TAIL_PARTIAL
-  if (!fin.o0 && !fin_in) in_moments_final<2><<<dim3((C + 15) / 16, N), TPB, 0, st>>>(workspace, chunks, C, HW, 0.f, a_mean, b2_mean, bs_mean);
-  // the affine gradients (and the copy gbs = gb2) are written by block 0 of the apply kernel
-  const int64_t total = (int64_t)N * HW * C;
-#define TAIL_APPLY(V, R, HSF, AM)                                                                                       \
-  restail_bwd_apply<V, R, HSF, AM><<<img_grid((int64_t)HW * (C / V), N), TPB, 0, st>>>(gout, out, t, a_mean, b2_mean, bs_mean, gy2, gs, \
-                                                                               HW, C, slope, N, gg2, gb2, ms ? ggs : nullptr,  \
-                                                                               ms ? gbs : nullptr, amax)
-#define TAIL_APPLY_AM(V, R, HSF) do { if (amax) TAIL_APPLY(V, R, HSF, true); else TAIL_APPLY(V, R, HSF, false); } while (0)
-#define TAIL_APPLY_MP(HSF, AM)                                                                                              \
-  restail_bwd_apply<4, true, HSF, AM, true><<<img_grid((int64_t)HW * (C / 4), N), TPB, 0, st>>>(gout, out, t, a_mean, b2_mean, bs_mean, gy2, \
-                                                                                             gs, HW, C, slope, N, gg2, gb2, ggs, gbs, amax, mrv)
-  if (mr) {
-    if (hs) { if (amax) TAIL_APPLY_MP(true, true); else TAIL_APPLY_MP(true, false); }
-    else { if (amax) TAIL_APPLY_MP(false, true); else TAIL_APPLY_MP(false, false); }
-  } else
-  if (hs) TAIL_APPLY_AM(4, true, true);
-  else if (C % 4 == 0) { if (remask) TAIL_APPLY_AM(4, true, false); else TAIL_APPLY_AM(4, false, false); }
-  else { if (remask) TAIL_APPLY_AM(1, true, false); else TAIL_APPLY_AM(1, false, false); }
-#undef TAIL_APPLY_MP
-#undef TAIL_APPLY_AM
-#undef TAIL_APPLY
-  SMSUT_LAUNCH_CHECK();
-  return SMSUT_OK;
+  TailCall c = tail_call(TailRef{(const float*)y2, m2, r2, g2, b2, (const float*)s, ms, rs, gs, bs}, N, HW, C, slope, stream);
+  c.y = out; c.hs = true;
+  return run_tail_fwd(c);
 }
 // The tail of an encoder level's block + the level's MaxPool2d(2, 2) (r05, reference network/blocks.py:74-79 + 131-133 / network/ugan.py:36-39).
 // Forward: out [N,H,W,C] (the skip connection), pooled [N,H/2,W/2,C] and idx [N,H/2,W/2,C] bytes (position of the maximum in its
@@ -1271,37 +1343,27 @@ static int restail_bwd_launch(const float* gout, const float* out, const float* 
 int smsut_restail_fwd_pool(const void* y2, const float* m2, const float* r2, const float* g2, const float* b2, const void* s,
                            const float* ms, const float* rs, const float* gs, const float* bs, float* out, float* pooled,
                            void* idx, int N, int H, int W, int C, float slope, int hs, void* stream) {
-  SMSUT_REQUIRE(y2 && m2 && r2 && g2 && b2 && s && ms && rs && gs && bs && out && pooled && N > 0 && H > 0 && W > 0 && C > 0 &&
-                C % 4 == 0 && !(H & 1) && !(W & 1) && (int64_t)H * W * C < (1ll << 31));
-  TailRef t{(const float*)y2, m2, r2, g2, b2, (const float*)s, ms, rs, gs, bs};
-  hipStream_t st = (hipStream_t)stream;
-  const dim3 g = img_grid((int64_t)(H / 2) * (W / 2) * (C / 4), N);
-  if (hs) restail_fwd_pool<true><<<g, TPB, 0, st>>>(t, out, pooled, (unsigned int*)idx, H, W, C, slope);
-  else restail_fwd_pool<false><<<g, TPB, 0, st>>>(t, out, pooled, (unsigned int*)idx, H, W, C, slope);
-  SMSUT_LAUNCH_CHECK();
-  return SMSUT_OK;
+  SMSUT_REQUIRE(ms && rs && gs && bs && pooled && H > 0 && W > 0 && C > 0 && C % 4 == 0 && !(H & 1) && !(W & 1) &&
+                (int64_t)H * W * C < (1ll << 31));
+  TailCall c = tail_call(TailRef{(const float*)y2, m2, r2, g2, b2, (const float*)s, ms, rs, gs, bs}, N, H * W, C, slope, stream);
+  c.y = out; c.pooled = pooled; c.idx = (unsigned int*)idx; c.W = W; c.hs = hs != 0;
+  return run_tail_fwd(c);
 }
-// Backward of that pair: gout = gradient of `out` through the skip connection, gp [N,H/2,W/2,C] = gradient of `pooled`; the block
-// output's total gradient (what smsut_maxpool2_bwd_add would write) is formed while loading, in both passes of the tail backward --
-// no pooling-backward pass, no full-resolution gradient tensor.  tickets (nullable): in-launch finalize as smsut_restail_bwd_fin;
-// amax (nullable): as smsut_restail_bwd_amax; hs: y2 / s fp16 as smsut_restail_bwd_hs.  Results bit-identical to
-// smsut_maxpool2_bwd_add followed by the corresponding smsut_restail_bwd* call.
-int smsut_restail_bwd_pool(const float* gout, const float* gp, const void* idx, const void* y2, const float* m2, const float* r2,
-                           const float* g2, const float* b2, const void* s, const float* ms, const float* rs, const float* gs_,
-                           const float* bs, float* gy2, float* gs, float* a_mean, float* b2_mean, float* bs_mean, float* gg2,
-                           float* gb2, float* ggs, float* gbs, float* workspace, int* tickets, float* amax, int N, int H, int W, int C,
-                           float slope, int hs, void* stream) {
-  SMSUT_REQUIRE(gp && H > 0 && W > 0 && C > 0 && !(H & 1) && !(W & 1) && (int64_t)H * W * C < (1ll << 31));
-  const MaxRef mr{gp, (const unsigned int*)idx, W};
-  return restail_bwd_launch(gout, gout, (const float*)y2, m2, r2, g2, b2, (const float*)s, ms, rs, gs_, bs, gy2, gs, a_mean, b2_mean,
-                            bs_mean, gg2, gb2, ggs, gbs, workspace, amax, N, H * W, C, slope, stream, hs != 0, tickets, &mr);
-}
+
+// Backward of the tail.  workspace: float[N * smsut_in_chunks(N,HW,C) * C * 3]; a/b2/bs: [N,C] scratch outputs;
+// b2 / bs (the two IN betas, nullable): with ms and both betas the activation mask is recomputed from y2 and s and `out`
+// is not read (8 tensor passes instead of 10); otherwise the mask is the sign of `out`.
+// gy2, gs: gradients w.r.t. the two raw conv outputs (gs = gradient of the identity when ms == null);
+// gg2/gb2/ggs/gbs: affine gradients (ggs/gbs nullable when ms == null).
 int smsut_restail_bwd(const float* gout, const float* out, const float* y2, const float* m2, const float* r2,
                       const float* g2, const float* b2, const float* s, const float* ms, const float* rs,
                       const float* gs_, const float* bs, float* gy2, float* gs, float* a_mean, float* b2_mean, float* bs_mean, float* gg2, float* gb2, float* ggs,
                       float* gbs, float* workspace, int N, int HW, int C, float slope, void* stream) {
-  return restail_bwd_launch(gout, out, y2, m2, r2, g2, b2, s, ms, rs, gs_, bs, gy2, gs, a_mean, b2_mean, bs_mean, gg2, gb2, ggs, gbs,
-                            workspace, nullptr, N, HW, C, slope, stream);
+  TailCall c = tail_call(TailRef{y2, m2, r2, g2, b2, s, ms, rs, gs_, bs}, N, HW, C, slope, stream);
+  c.gout = gout; c.out = out; c.workspace = workspace;
+  c.gy2 = gy2; c.gs = gs; c.a_mean = a_mean; c.b2_mean = b2_mean; c.bs_mean = bs_mean;
+  c.gg2 = gg2; c.gb2 = gb2; c.ggs = ggs; c.gbs = gbs;
+  return run_tail_bwd(c);
 }
 // ... with the per-image means finalised INSIDE the partial-sum launch (common.h: write-through partials, agent-scope ticket per
 // image, the last-arriving workgroup combines in in_moments_final<2>'s order: same bits) -- two launches instead of three.
@@ -1312,8 +1374,11 @@ int smsut_restail_bwd_fin(const float* gout, const float* out, const float* y2, 
                           const float* gs_, const float* bs, float* gy2, float* gs, float* a_mean, float* b2_mean, float* bs_mean, float* gg2, float* gb2, float* ggs,
                           float* gbs, float* workspace, int* tickets, int N, int HW, int C, float slope, void* stream) {
   SMSUT_REQUIRE(tickets);
-  return restail_bwd_launch(gout, out, y2, m2, r2, g2, b2, s, ms, rs, gs_, bs, gy2, gs, a_mean, b2_mean, bs_mean, gg2, gb2, ggs, gbs,
-                            workspace, nullptr, N, HW, C, slope, stream, false, tickets);
+  TailCall c = tail_call(TailRef{y2, m2, r2, g2, b2, s, ms, rs, gs_, bs}, N, HW, C, slope, stream);
+  c.gout = gout; c.out = out; c.workspace = workspace; c.tickets = tickets;
+  c.gy2 = gy2; c.gs = gs; c.a_mean = a_mean; c.b2_mean = b2_mean; c.bs_mean = bs_mean;
+  c.gg2 = gg2; c.gb2 = gb2; c.ggs = ggs; c.gbs = gbs;
+  return run_tail_bwd(c);
 }
 // ... that also hands over max |gy2| (amax[0 .. B)) and max |gs| (amax[B .. 2B)), B = smsut_amax_blocks, for smsut_absmax_finish
 int smsut_restail_bwd_amax(const float* gout, const float* out, const float* y2, const float* m2, const float* r2,
@@ -1321,8 +1386,11 @@ int smsut_restail_bwd_amax(const float* gout, const float* out, const float* y2,
                            const float* gs_, const float* bs, float* gy2, float* gs, float* a_mean, float* b2_mean, float* bs_mean, float* gg2, float* gb2, float* ggs,
                            float* gbs, float* workspace, float* amax, int N, int HW, int C, float slope, void* stream) {
   SMSUT_REQUIRE(amax);
-  return restail_bwd_launch(gout, out, y2, m2, r2, g2, b2, s, ms, rs, gs_, bs, gy2, gs, a_mean, b2_mean, bs_mean, gg2, gb2, ggs, gbs,
-                            workspace, amax, N, HW, C, slope, stream);
+  TailCall c = tail_call(TailRef{y2, m2, r2, g2, b2, s, ms, rs, gs_, bs}, N, HW, C, slope, stream);
+  c.gout = gout; c.out = out; c.workspace = workspace; c.amax = amax;
+  c.gy2 = gy2; c.gs = gs; c.a_mean = a_mean; c.b2_mean = b2_mean; c.bs_mean = bs_mean;
+  c.gg2 = gg2; c.gb2 = gb2; c.ggs = ggs; c.gbs = gbs;
+  return run_tail_bwd(c);
 }
 // "half storage" (config 5): y2 and s are fp16 [N,HW,C]; two-IN tail with both betas (the mask is recomputed, `out` is not read),
 // C % 4 == 0; amax nullable (see smsut_restail_bwd_amax)
@@ -1331,8 +1399,29 @@ int smsut_restail_bwd_hs(const float* gout, const float* out, const void* y2, co
                          const float* gs_, const float* bs, float* gy2, float* gs, float* a_mean, float* b2_mean, float* bs_mean, float* gg2, float* gb2, float* ggs,
                          float* gbs, float* workspace, float* amax, int N, int HW, int C, float slope, void* stream) {
   SMSUT_REQUIRE(ms && b2 && bs && C % 4 == 0);
-  return restail_bwd_launch(gout, out, (const float*)y2, m2, r2, g2, b2, (const float*)s, ms, rs, gs_, bs, gy2, gs, a_mean, b2_mean,
-                            bs_mean, gg2, gb2, ggs, gbs, workspace, amax, N, HW, C, slope, stream, true);
+  TailCall c = tail_call(TailRef{(const float*)y2, m2, r2, g2, b2, (const float*)s, ms, rs, gs_, bs}, N, HW, C, slope, stream);
+  c.gout = gout; c.out = out; c.workspace = workspace; c.amax = amax; c.hs = true;
+  c.gy2 = gy2; c.gs = gs; c.a_mean = a_mean; c.b2_mean = b2_mean; c.bs_mean = bs_mean;
+  c.gg2 = gg2; c.gb2 = gb2; c.ggs = ggs; c.gbs = gbs;
+  return run_tail_bwd(c);
+}
+// Backward of smsut_restail_fwd_pool: gout = gradient of `out` through the skip connection, gp [N,H/2,W/2,C] = gradient of `pooled`;
+// the block output's total gradient (what smsut_maxpool2_bwd_add would write) is formed while loading, in both passes of the tail
+// backward -- no pooling-backward pass, no full-resolution gradient tensor.  tickets (nullable): in-launch finalize as
+// smsut_restail_bwd_fin; amax (nullable): as smsut_restail_bwd_amax; hs: y2 / s fp16 as smsut_restail_bwd_hs.  Results bit-identical
+// to smsut_maxpool2_bwd_add followed by the corresponding smsut_restail_bwd* call.
+int smsut_restail_bwd_pool(const float* gout, const float* gp, const void* idx, const void* y2, const float* m2, const float* r2,
+                           const float* g2, const float* b2, const void* s, const float* ms, const float* rs, const float* gs_,
+                           const float* bs, float* gy2, float* gs, float* a_mean, float* b2_mean, float* bs_mean, float* gg2,
+                           float* gb2, float* ggs, float* gbs, float* workspace, int* tickets, float* amax, int N, int H, int W, int C,
+                           float slope, int hs, void* stream) {
+  SMSUT_REQUIRE(gp && H > 0 && W > 0 && C > 0 && !(H & 1) && !(W & 1) && (int64_t)H * W * C < (1ll << 31));
+  TailCall c = tail_call(TailRef{(const float*)y2, m2, r2, g2, b2, (const float*)s, ms, rs, gs_, bs}, N, H * W, C, slope, stream);
+  c.gout = gout; c.out = gout; c.workspace = workspace; c.tickets = tickets; c.amax = amax; c.hs = hs != 0;
+  c.mr = MaxRef{gp, (const unsigned int*)idx, W};
+  c.gy2 = gy2; c.gs = gs; c.a_mean = a_mean; c.b2_mean = b2_mean; c.bs_mean = bs_mean;
+  c.gg2 = gg2; c.gb2 = gb2; c.ggs = ggs; c.gbs = gbs;
+  return run_tail_bwd(c);
 }
 
 }  // extern "C"
