@@ -687,6 +687,18 @@ int smsut_surface_stats_sp(const uint8_t* pred, const uint8_t* gt, double* out, 
 int64_t smsut_surface_hd_sp_ws(int D, int H, int W, int n_cls, int planar);
 int smsut_surface_hd_sp(const uint8_t* pred, const uint8_t* gt, double* out, void* workspace, int D, int H, int W, int n_cls,
                         int planar, double quantile, double sz, double sy, double sx, void* stream);
+/* Validation on the device (csrc/evaluate.hip): the prediction map of a batch of logits and the Dice overlap counts of its slices in
+ * one pass.  logits: NHWC [N][HW][C] fp32; labels: int64 [N][HW]; vol: int [N], the volume slot of each slice.
+ *   prediction p = the first maximum of channels 0 .. K-1 of the pixel's C-float row (K < C: head 0 of CoraNet's 3L+1 channels),
+ *     by smsut_argmax_channels' comparison: the first maximum wins, a NaN wins.  pred: uint8 [N][HW], nullable.
+ *   counts: int64 [V][K][3] = {|P & G|, |P|, |G|} per (volume, class), ACCUMULATED and never zeroed here: counts[vol][p][1] += 1;
+ *     a label g in 0 .. K-1 adds to counts[vol][g][2] and, when p == g, to counts[vol][p][0]; any other label counts nowhere.
+ *   A slice with vol[n] < 0 or vol[n] >= V is skipped: no count, its pred bytes untouched.
+ * Integer arithmetic only (register counters, a block reduction, one 64-bit integer atomic add per non-zero (class, statistic) and
+ * workgroup): bitwise reproducible.  Needs 1 <= K <= C, K <= 32, HW >= 1, V >= 1, N <= 65535, otherwise SMSUT_EINVAL and nothing
+ * is launched; N == 0 returns SMSUT_OK without a launch. */
+int smsut_eval_overlap(const float* logits, const int64_t* labels, const int* vol, int64_t* counts, uint8_t* pred /*nullable*/, int N,
+                       int64_t HW, int C, int K, int V, void* stream);
 
 #ifdef __cplusplus
 }

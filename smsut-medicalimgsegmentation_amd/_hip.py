@@ -238,6 +238,8 @@ SIGNATURES: Dict[str, str] = {
     "smsut_surface_stats_sp": "pppp iiiii ddd s",
     "smsut_surface_hd_sp_ws": "iiiii",
     "smsut_surface_hd_sp": "pppp iiiii d ddd s",
+    # evaluate.hip (validation)
+    "smsut_eval_overlap": "ppppp i l iii s",
 }
 _RET_I64 = {"smsut_wino_image_floats", "smsut_conv2d_wgrad_pair_ws", "smsut_convT2x2_wgrad_ps_ws", "smsut_conv2d_wgrad_sc_ws", "smsut_conv2d_k4_wgrad_ws", "smsut_conv2d_wgrad_f16_ws", "smsut_conv2d_wgrad_sc_f16_ws", "smsut_absmax_scale_ws", "smsut_conv2d_wgrad_generic_ws", "smsut_colsum_ws", "smsut_dicece_ws", "smsut_sum_ws",
             "smsut_conv2d_wgrad_mfma_ws", "smsut_convT2x2_wgrad_mfma_ws", "smsut_conv2d_flat_wgrad_ws", "smsut_conv1x1_wgrad_ws",

@@ -54,6 +54,8 @@ split_yaml = "semi-1910.yaml"  # config.py:54
 test_hausdorff = False         # -p test also writes {modality}_hd_matrix.csv (Hausdorff and HD95; commented out upstream)
 test_spacing = None            # voxel spacing of the -p test surface distances: None (voxels), one (sz, sy, sx) for every volume,
                                # or a mapping {volume key such as 'ct_001', or modality name such as 'ct': (sz, sy, sx)}
+validate_on_device = False     # validation and -p test without the host in the loop: argmax + Dice overlap counts in one launch per
+                               # batch, nothing read back before the loader is exhausted (csrc/evaluate.hip; same Dice, meter and files)
 data_aug = dict(               # config.py:60-71
     rotate=True, rotate_degrees=15,
     resizeCrop=True, resizeCrop_size=input_size,

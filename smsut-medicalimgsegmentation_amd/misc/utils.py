@@ -57,10 +57,98 @@ def _full_matrix(matrix, n):
     return full
 
 
+def dice_matrix_from_counts(keys, counts):
+    """``get_mo_matrix`` from overlap counts instead of volumes.  ``keys``: the volume keys 'm_pid' in slot order; ``counts``:
+    an integer array [len(keys), K, 3] = {|P & G|, |P|, |G|} per (volume, class), class 0 the background (what
+    ``ops.eval_overlap`` accumulates; organ i is class i + 1, a class K does not reach scores 0.0 as it does there).  The
+    result is ``get_mo_matrix``'s bit for bit when the counts are those of the volumes it is given, in the same key order:
+    the same fp64 expression on equal integers, accumulated per modality in the same order, the same 1e-8 guard and means."""
+    counts = np.asarray(counts)
+    keys = list(keys)
+    if counts.dtype == np.bool_ or not np.issubdtype(counts.dtype, np.integer):
+        raise TypeError(f"dice_matrix_from_counts: expected integer counts, got {counts.dtype}")
+    if counts.ndim != 3 or counts.shape[0] != len(keys) or counts.shape[2] != 3:
+        raise ValueError(f"dice_matrix_from_counts: expected counts of shape [{len(keys)}, K, 3], got {counts.shape}")
+    matrix = np.zeros((cfg.n_modal, cfg.n_label))
+    n = np.zeros((cfg.n_modal, 1))
+    for slot, k in enumerate(keys):
+        m = cfg.Modality[k.split("_")[0]].value
+        for i in range(cfg.n_label):
+            inter, n_p, n_g = (int(v) for v in counts[slot, i + 1]) if i + 1 < counts.shape[1] else (0, 0, 0)
+            matrix[m][i] += 2.0 * inter / float(n_p + n_g) if n_p + n_g else 0.0
+        n[m] += 1
+    return _full_matrix(matrix, n)
+
+
+class DiceCounter:
+    """The Dice overlap counts of one validation pass, kept on the device.  A volume key 'm_pid' gets a slot in order of first
+    appearance (``keys``); ``update`` adds a batch's counts into int64 ``counts`` [slots, K, 3] with one ``ops.eval_overlap``
+    launch; ``matrix`` makes the one device-to-host copy.  The tensor is allocated at the first update (K = its class count),
+    zero-initialised, and doubled on the device when the slots run out: nothing waits for the device before ``matrix``."""
+
+    def __init__(self, slots=16):
+        self._slots = max(int(slots), 1)
+        self.keys = []
+        self.counts = None
+        self.classes = None
+        self._slot_of = {}
+        self._seen = set()
+
+    def update(self, logits, labels, names, classes=None, want_pred=False):
+        """Count one batch: ``names`` 'm_pid_z', one per slice of ``logits`` / ``labels`` (``ops.eval_overlap``'s arguments).
+        A name seen before raises ``ValueError``: the host path overwrites a repeated slice, counts would add it twice.
+        Returns the uint8 prediction with ``want_pred``, else None."""
+        import torch
+        from .. import ops
+        names = list(names)
+        fresh, keys = set(), []
+        for nm in names:
+            m, pid, _ = nm.split("_")
+            cfg.Modality[m]                                  # (KeyError now, not in matrix())
+            if nm in self._seen or nm in fresh:
+                raise ValueError(f"DiceCounter: slice {nm!r} was counted before")
+            fresh.add(nm)
+            keys.append(f"{m}_{pid}")
+        k = int(logits.shape[1] if classes is None else classes)
+        if self.classes is not None and k != self.classes:
+            raise ValueError(f"DiceCounter: {k} classes after {self.classes}")
+        n_new = len(set(keys) - set(self._slot_of))
+        if self.counts is None or len(self.keys) + n_new > self.counts.shape[0]:
+            size = self._slots if self.counts is None else self.counts.shape[0]
+            while size < len(self.keys) + n_new:
+                size *= 2
+            grown = torch.zeros(size, k, 3, dtype=torch.int64, device=logits.device)
+            if self.counts is not None:
+                grown[:self.counts.shape[0]] = self.counts
+            slot_of, key_list = dict(self._slot_of), list(self.keys)
+        else:
+            grown, slot_of, key_list = self.counts, dict(self._slot_of), list(self.keys)
+        for key in keys:
+            if key not in slot_of:
+                slot_of[key] = len(key_list)
+                key_list.append(key)
+        pred = ops.eval_overlap(logits, labels, [slot_of[key] for key in keys], grown, classes=k, want_pred=want_pred)
+        self.counts, self.classes, self._slot_of, self.keys = grown, k, slot_of, key_list     # (only once the launch is out)
+        self._seen |= fresh
+        return pred
+
+    def matrix(self):
+        """The modality x organ Dice matrix of everything counted so far (``dice_matrix_from_counts``)."""
+        if self.counts is None:
+            return dice_matrix_from_counts([], np.zeros((0, cfg.n_label + 1, 3), dtype=np.int64))
+        return dice_matrix_from_counts(self.keys, self.counts[:len(self.keys)].cpu().numpy())
+
+
 def _device_u8(a, what):
-    """An integer (or bool) NumPy array with values in 0..255 as a uint8 tensor on the current HIP device."""
+    """An integer (or bool) NumPy array with values in 0..255 as a uint8 tensor on the current HIP device.  A tensor is taken
+    as it is when it already is that -- uint8, on the current HIP device (volumes assembled there by
+    ``validate_epoch_device``) -- and any other tensor raises ``TypeError``: nothing is converted or moved silently."""
     import torch
     from .._hip import SmsutHipError
+    if isinstance(a, torch.Tensor):
+        if a.dtype != torch.uint8 or not a.is_cuda or a.device.index != torch.cuda.current_device():
+            raise TypeError(f"{what}: a tensor must be uint8 on the current HIP device, got {a.dtype} on {a.device}")
+        return a
     a = np.asarray(a)
     if a.dtype != np.bool_ and not np.issubdtype(a.dtype, np.integer):
         raise TypeError(f"{what}: expected an integer array, got {a.dtype}")

@@ -2057,6 +2057,55 @@ def argmax_channels(logits):
     return out
 
 
+EVAL_MAX_CLASSES, EVAL_MAX_SLICES = 32, 65535      # the limits of smsut_eval_overlap (include/smsut_hip.h)
+
+
+def eval_overlap(logits, labels, vol_ids, counts, classes=None, want_pred=True):
+    """Validation in one pass (csrc/evaluate.hip): the argmax of channels ``0 .. classes-1`` of every pixel (``argmax_channels``'
+    rule; ``classes`` defaults to all C channels, CoraNet passes L + 1: head 0 of its 3L+1) and the Dice overlap counts of the
+    batch, ADDED into ``counts``: int64 ``[V, classes, 3]`` = {|P & G|, |P|, |G|} per (volume slot, class), contiguous, on the
+    logits' device; the caller zeroes it once.  ``labels``: int64 ``[N, H, W]`` on the same device; a label outside
+    ``0 .. classes-1`` counts nowhere.  ``vol_ids``: N Python ints, the volume slot of each slice, or -1 for a slice to skip (no
+    count, its prediction bytes left as allocated); checked HERE, on the host, and uploaded as int32 -- no device value is read
+    back.  Returns the prediction as uint8 ``[N, H, W]``, or None with ``want_pred=False``.  Wrong types raise ``TypeError``,
+    wrong shapes or values ``ValueError``, before the device is touched."""
+    for what, t, dt in (("logits", logits, torch.float32), ("labels", labels, torch.int64), ("counts", counts, torch.int64)):
+        if not isinstance(t, torch.Tensor):
+            raise TypeError(f"eval_overlap: {what} must be a tensor, got {type(t).__name__}")
+        if t.dtype != dt:
+            raise TypeError(f"eval_overlap: {what} must be {dt}, got {t.dtype}")
+        if not t.is_cuda or t.device != logits.device:
+            raise TypeError(f"eval_overlap: {what} must be on the logits' HIP device, got {t.device} (no CPU fallback)")
+    if logits.dim() != 4:
+        raise ValueError(f"eval_overlap: expected NCHW logits, got shape {tuple(logits.shape)}")
+    n, c, h, w = logits.shape
+    k = c if classes is None else int(classes)
+    if not 1 <= k <= min(c, EVAL_MAX_CLASSES):
+        raise ValueError(f"eval_overlap: classes must lie in 1..min(C, {EVAL_MAX_CLASSES}), got {k} with C = {c}")
+    if tuple(labels.shape) != (n, h, w):
+        raise ValueError(f"eval_overlap: labels must be [N, H, W] = {(n, h, w)}, got {tuple(labels.shape)}")
+    if counts.dim() != 3 or counts.shape[0] < 1 or tuple(counts.shape[1:]) != (k, 3) or not counts.is_contiguous():
+        raise ValueError(f"eval_overlap: counts must be a contiguous [V >= 1, {k}, 3] tensor, got {tuple(counts.shape)}")
+    if n > EVAL_MAX_SLICES or h * w < 1:
+        raise ValueError(f"eval_overlap: needs at most {EVAL_MAX_SLICES} slices of at least one pixel, got {(n, h, w)}")
+    ids = [int(i) for i in vol_ids]
+    if len(ids) != n:
+        raise ValueError(f"eval_overlap: {len(ids)} volume ids for {n} slices")
+    n_vol = counts.shape[0]
+    for i in ids:
+        if not -1 <= i < n_vol:
+            raise ValueError(f"eval_overlap: volume id {i} is neither -1 nor a slot of counts ({n_vol} slots)")
+    pred = torch.empty(n, h, w, dtype=torch.uint8, device=logits.device) if want_pred else None
+    if n == 0:
+        return pred
+    z = nhwc(logits.detach())
+    # (pinned + non_blocking: a pageable upload would make the host wait for the stream; the pinned block is recycled by torch's
+    #  host allocator only after the copy has run)
+    vol = torch.tensor(ids, dtype=torch.int32).pin_memory().to(z.device, non_blocking=True)
+    H.call("smsut_eval_overlap", z, labels.contiguous(), vol, counts, pred, n, h * w, c, k, n_vol, _s())
+    return pred
+
+
 # ------------------------------------------------------------------------------------------- CoraNet heads
 # The 3L+1 channels of the CoraNet U-Net are three (L+1)-class heads sharing the background logit (channel 0; head k owns channels
 # 1+kL .. (k+1)L, reference trainer/coraNetTrainer.py:288-295).  These ops take the network's NHWC output as it is -- no concatenated

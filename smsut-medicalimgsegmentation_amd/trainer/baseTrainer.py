@@ -334,9 +334,7 @@ class BaseTrainer(abc.ABC):
             self.info("[TRN] Epoch: %d/%d, elapsed: %.2fs,%s" % (epoch, cfg.max_epoch, time.time() - tic, train_meter))
             tic = time.time()
             test_meter.reset_cur()
-            gt = self._collect_labels(test)
-            n_prd, prd = self.validate_epoch(test, gt, test_meter)
-            dices = self.validate_dice(prd, gt)
+            dices = self._validation_dices(test, test_meter)
             test_meter.accumulate(dices, {k: 1.0 for k in dices})
             test_meter.update_cur()
             self.info("[TST] Epoch: %d/%d, elapsed: %.2fs,%s" % (epoch, cfg.max_epoch, time.time() - tic, test_meter))
@@ -355,6 +353,16 @@ class BaseTrainer(abc.ABC):
         box = [bool(flag)]
         dist.broadcast_object_list(box, src=0, group=self.group)
         return box[0]
+
+    def _validation_dices(self, test, test_meter):
+        """One validation pass over ``test``: the losses go into ``test_meter``, the Dice dict comes back.  On the host (label
+        pass, per-batch read-back, NumPy Dice) or, with ``cfg.validate_on_device``, on the device (``validate_epoch_device``)."""
+        if cfg.validate_on_device:
+            _, counter = self.validate_epoch_device(test, test_meter)
+            return self.validate_dice_device(counter)
+        gt = self._collect_labels(test)
+        n_prd, prd = self.validate_epoch(test, gt, test_meter)
+        return self.validate_dice(prd, gt)
 
     @staticmethod
     def _collect_labels(loader):
@@ -407,6 +415,81 @@ class BaseTrainer(abc.ABC):
         d["dice"] = mo[-1, -1]
         return d
 
+    # ------------------------------------------------------------------ validation on the device (cfg.validate_on_device)
+    def _eval_loss(self, out, msk):
+        """``(validation loss of one batch, class count of the prediction or None for all channels)``: the one thing a
+        trainer with another validation loss or head layout overrides (coraNetTrainer)."""
+        return self.loss(out, msk), None
+
+    def validate_epoch_device(self, loader, meter=None, keep_volumes=False):
+        """``validate_epoch`` without the host in the loop: the same batches, the same zero-padding of a short batch to
+        cfg.batch_size and crop back, the same loss -- but the loss scalar stays on the device, prediction and Dice counting
+        are one launch (``DiceCounter.update`` -> ``ops.eval_overlap``) and nothing is read back until the loader is
+        exhausted.  Then ONE stacked copy brings the losses over and the meter is fed in batch order with the arguments
+        ``validate_epoch`` gives it: the padded ``img.size(0)`` and ``mdl[0].item()`` of the loader's host tensor.  No
+        ground-truth pass (``_collect_labels``) is needed: a slice is paired with its label inside its own batch.
+
+        Returns ``(n_prd, counter)``; with ``keep_volumes`` also ``(..., prd, gt)``: {volume key: uint8 [D, H, W] tensor on the
+        device}, one gather per volume, slices ordered by z, keys in order of first appearance.
+
+        Equivalence with the host path.  It holds for loaders whose names carry z = 0 .. D-1 once each per volume (both of the
+        project's loaders do).  Under that condition the Dice dict (``validate_dice_device``), the meter and the bytes of
+        the CSV files ``test`` writes are identical to the host path's: both run the same deterministic forward kernels on
+        the same inputs, the prediction is ``argmax_channels``' to the bit, and the matrix is the same fp64 arithmetic on
+        equal integers.  Slices are paired with their labels per batch, not by volume index: a repeated name raises
+        ``ValueError`` here, where the host path would overwrite the earlier slice."""
+        from ..misc.utils import DiceCounter
+        self.net.eval()
+        counter, n_prd = DiceCounter(), 0
+        losses, meter_args = [], []
+        preds, gts, where, lab_range = [], [], {}, None
+        with torch.no_grad():
+            for img, msk, mdl, inm in loader:
+                b, c, h, w = img.shape
+                img = img.to(self.device)
+                if b != cfg.batch_size:
+                    img = torch.cat([img, torch.zeros(cfg.batch_size - b, c, h, w, device=self.device)], 0)
+                out = self._forward_eval(img)
+                if b != cfg.batch_size:
+                    out = out[:b]
+                msk = msk.to(self.device)
+                loss, classes = self._eval_loss(out, msk)
+                if meter is not None:
+                    losses.append(loss.detach().reshape(-1)[0])
+                    meter_args.append((mdl[0].item(), img.size(0)))
+                pred = counter.update(out, msk, inm[:b], classes=classes, want_pred=keep_volumes)
+                if keep_volumes:
+                    for i in range(b):
+                        m, pid, z = inm[i].split("_")
+                        where.setdefault(f"{m}_{pid}", []).append((int(z), n_prd + i))
+                    preds.append(pred)
+                    gts.append(msk.to(torch.uint8))
+                    lo_hi = torch.stack([-msk.amin(), msk.amax()])
+                    lab_range = lo_hi if lab_range is None else torch.maximum(lab_range, lo_hi)
+                n_prd += b
+        if losses:
+            for v, (modal, n) in zip(torch.stack(losses).tolist(), meter_args):
+                meter.accumulate(*meter.collect_loss_by(v, modal, n))
+        if not keep_volumes:
+            return n_prd, counter
+        prd, gt = {}, {}
+        if preds:
+            lo, hi = lab_range.tolist()                     # (the uint8 cast above wraps: refuse what the host path refuses)
+            if -lo < 0 or hi > 255:
+                raise ValueError(f"ground truth: values must lie in 0..255 (got {-lo}..{hi})")
+            all_p, all_g = torch.cat(preds), torch.cat(gts)
+            for key, zs in where.items():
+                idx = torch.tensor([j for _, j in sorted(zs)], dtype=torch.int64).pin_memory().to(self.device, non_blocking=True)
+                prd[key], gt[key] = all_p.index_select(0, idx), all_g.index_select(0, idx)
+        return n_prd, counter, prd, gt
+
+    def validate_dice_device(self, counter):
+        """``validate_dice`` from a ``DiceCounter``: the same dict."""
+        mo = counter.matrix()
+        d = {f"dice_{i}": mo[i, -1] for i in range(cfg.n_modal)}
+        d["dice"] = mo[-1, -1]
+        return d
+
     def test(self, loader_type, expr_root):
         """baseTrainer.py:254-318: the raw Dice matrix (``dice_matrix.csv``, returned) and the reference's test table
         ``{modality}_trois_matrix.csv`` -- the Dice rows, an empty line, then the ASSD rows of ``get_all_matrix`` (connected-
@@ -416,9 +499,15 @@ class BaseTrainer(abc.ABC):
         With ``cfg.test_spacing`` (one (sz, sy, sx), or a mapping by volume key or modality name) the ASSD, Hausdorff and HD95
         rows are in that spacing's unit and the log says which spacing was used; None: voxels, the same bytes as ever."""
         _, _, loader = self.get_loaders(loader_type)
-        gt = self._collect_labels(loader)
-        n, prd = self.validate_epoch(loader, gt)
-        mo = get_mo_matrix(prd, gt)
+        if cfg.validate_on_device:
+            # counts and volumes stay on the device: ``dice_matrix.csv`` from the counts, the cleanup and surface kernels on the
+            # volumes as assembled there; predictions leave the GPU only as the matrices below
+            n, counter, prd, gt = self.validate_epoch_device(loader, keep_volumes=True)
+            mo = counter.matrix()
+        else:
+            gt = self._collect_labels(loader)
+            n, prd = self.validate_epoch(loader, gt)
+            mo = get_mo_matrix(prd, gt)
         maybe_mkdir(expr_root)
         np.savetxt(pjoin(expr_root, "dice_matrix.csv"), mo, delimiter=",", fmt="%.6f")
         spacing = {} if cfg.test_spacing is None else {"spacings": cfg.test_spacing}

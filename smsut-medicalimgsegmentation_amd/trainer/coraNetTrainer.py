@@ -212,9 +212,7 @@ class coraNetTrainer(BaseTrainer):
 
     def _validate(self, test, test_meter, tag, epoch, n_epochs, tic):
         test_meter.reset_cur()
-        gt = self._collect_labels(test)
-        _, prd = self.validate_epoch(test, gt, test_meter)
-        dices = self.validate_dice(prd, gt)
+        dices = self._validation_dices(test, test_meter)
         test_meter.accumulate(dices, {k: 1.0 for k in dices})
         test_meter.update_cur()
         self.info("[TST] %sEpoch: %d/%d, elapsed: %.2fs,%s" % (tag, epoch, n_epochs, time.time() - tic, test_meter))
@@ -292,6 +290,10 @@ class coraNetTrainer(BaseTrainer):
                     prd[f"{m}_{pid}"][int(z)] = pred[i]
                     n_prd += 1
         return n_prd, prd
+
+    def _eval_loss(self, out, msk):
+        """``validate_epoch_device``'s hook: the three-head supervised loss, and head 0 (channels 0 .. L of the 3L+1) predicts."""
+        return self.sup_loss(out, msk)[0], (out.shape[1] - 1) // 3 + 1
 
     def save_pseudo(self, loader_type, expr_root):
         """``-p pseudo``: pseudo labels and certainty masks of the unlabelled slices as ``pseudo/{plab,mask}.npy`` (uint8)."""
