@@ -699,6 +699,20 @@ int smsut_surface_hd_sp(const uint8_t* pred, const uint8_t* gt, double* out, voi
  * is launched; N == 0 returns SMSUT_OK without a launch. */
 int smsut_eval_overlap(const float* logits, const int64_t* labels, const int* vol, int64_t* counts, uint8_t* pred /*nullable*/, int N,
                        int64_t HW, int C, int K, int V, void* stream);
+/* Translation metrics of the test phase (csrc/similarity.hip): SSIM, squared and absolute error of two image batches in one pass.
+ * a, b: fp32 [n][h][w], dense.  out: double [n][3], WRITTEN (not accumulated), per slice
+ *   {sum of SSIM over its (h-10)(w-10) window centres, SE = sum over all h w pixels of (a-b)^2, AE = sum of |a-b|}.
+ *   SSIM (Wang et al. 2004): the 11x11 window w (x) w, w[k] = exp(-k^2 / (2 1.5^2)), k = -5 .. 5, normalised to sum 1; population
+ *   moments mu_a, mu_b, s_a^2 = E[a^2] - mu_a^2, s_b^2, s_ab = E[ab] - mu_a mu_b at every centre at least 5 pixels from each edge;
+ *   ((2 mu_a mu_b + C1)(2 s_ab + C2)) / ((mu_a^2 + mu_b^2 + C1)(s_a^2 + s_b^2 + C2)), C1 = (0.01 data_range)^2, C2 = (0.03 data_range)^2.
+ *   Window sums (11 fp32 weights, fixed tap order) and the per-centre value are fp32; SE and AE convert each pixel to fp64 before
+ *   the subtraction; every sum over centres or pixels is fp64 in a fixed order, without atomics: bitwise reproducible.
+ *   A NaN or Inf in one slice stays in that slice's three outputs.
+ * workspace: smsut_image_similarity_ws(n, h, w) bytes (per-workgroup partials), -1 for arguments outside the limits.
+ * Limits: 1 <= n <= 65535, 11 <= h, w <= 4096, data_range finite and positive; otherwise SMSUT_EINVAL and nothing is launched. */
+int64_t smsut_image_similarity_ws(int n, int h, int w);
+int smsut_image_similarity(const float* a, const float* b, double* out, void* workspace, int n, int h, int w, double data_range,
+                           void* stream);
 
 #ifdef __cplusplus
 }

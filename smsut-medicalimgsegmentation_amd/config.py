@@ -56,6 +56,11 @@ test_spacing = None            # voxel spacing of the -p test surface distances:
                                # or a mapping {volume key such as 'ct_001', or modality name such as 'ct': (sz, sy, sx)}
 validate_on_device = False     # validation and -p test without the host in the loop: argmax + Dice overlap counts in one launch per
                                # batch, nothing read back before the loader is exhausted (csrc/evaluate.hip; same Dice, meter and files)
+test_translation = False       # ugan trainers: -p test also writes {modality}_translation_matrix.csv (SSIM / PSNR / MAE of the translator's
+                               # cycle x -> G(x, i->j) -> G(., j->i) and of its paired translations; csrc/similarity.hip, nothing read back
+                               # before the loader is exhausted)
+test_translation_pairs = (('t1in', 't1out'),)   # modality-name pairs whose slices a_pid_z / b_pid_z show the same anatomy (CHAOS t1in /
+                               # t1out are registered acquisitions); a pair whose modalities or slices are not in the test set adds nothing
 data_aug = dict(               # config.py:60-71
     rotate=True, rotate_degrees=15,
     resizeCrop=True, resizeCrop_size=input_size,

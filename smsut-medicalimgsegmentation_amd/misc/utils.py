@@ -3,7 +3,9 @@
 formula (medpy is a third-party dependency that is not installed here; SURVEY.md 8c: parity unpinned), and the test
 table of ``get_all_matrix`` (:206-283) with ``connected_components`` (:18-36) and medpy's ``assd`` restated on the GPU
 (csrc/metrics.hip; skimage and medpy are not installed here either, the same unpinned parity); and medpy's ``hd`` / ``hd95`` /
-``asd`` with ``get_hd_matrix``, the Hausdorff table the reference imported ``hd`` for and then left out."""
+``asd`` with ``get_hd_matrix``, the Hausdorff table the reference imported ``hd`` for and then left out; and, with no counterpart
+upstream, the translator's metrics: ``ssim`` / ``psnr`` / ``mae``, ``TranslationMeter`` and ``translation_tables``
+(csrc/similarity.hip)."""
 import os
 from collections import OrderedDict
 from copy import deepcopy
@@ -373,6 +375,148 @@ def get_all_matrix(prd_npys, gt_npys, spacings=None):
 def matrix_text(matrix):
     """Rows of '%.4f' values joined by ',' (the layout of the reference's ``{modality}_trois_matrix.csv``)."""
     return "".join(",".join("%.4f" % v for v in row) + "\n" for row in matrix)
+
+
+# ------------------------------------------------------------------------------------------- translation metrics (test phase)
+# SSIM (Wang et al. 2004: 11x11 Gaussian window, sigma 1.5, population moments; what skimage's structural_similarity computes with
+# gaussian_weights=True, sigma=1.5, use_sample_covariance=False -- skimage is not installed here: parity unpinned), PSNR and MAE of
+# the unified translator's images, from the three per-slice sums of ``ops.image_similarity`` (csrc/similarity.hip).
+def _device_f32(a, what):
+    """A NumPy array of numbers as a float32 tensor on the current HIP device.  A tensor is taken as it is when it already is
+    that -- float32 on a HIP device -- and any other tensor raises ``TypeError``: nothing is converted or moved silently."""
+    import torch
+    from .._hip import SmsutHipError
+    if isinstance(a, torch.Tensor):
+        if a.dtype != torch.float32 or not a.is_cuda:
+            raise TypeError(f"{what}: a tensor must be float32 on a HIP device, got {a.dtype} on {a.device}")
+        return a
+    a = np.asarray(a)
+    if a.dtype == np.bool_ or not (np.issubdtype(a.dtype, np.floating) or np.issubdtype(a.dtype, np.integer)):
+        raise TypeError(f"{what}: expected an array of numbers, got {a.dtype}")
+    if not torch.cuda.is_available():
+        raise SmsutHipError("the translation metrics run on an MI355X (no HIP device visible; there is no CPU fallback)")
+    return torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(torch.device("cuda", torch.cuda.current_device()))
+
+
+def _similarity_sums(a, b, data_range, what):
+    """``(rows, h, w)``: the [D, 3] host array of ``ops.image_similarity`` for one image [H, W] or one volume [D, H, W]."""
+    from .. import ops
+    if np.ndim(a) not in (2, 3) or tuple(np.shape(a)) != tuple(np.shape(b)):
+        raise ValueError(f"{what}: expected two [H, W] images or [D, H, W] volumes of one shape, got {tuple(np.shape(a))} and "
+                         f"{tuple(np.shape(b))}")
+    ta, tb = _device_f32(a, what), _device_f32(b, what)
+    h, w = ta.shape[-2:]
+    rows = ops.image_similarity(ta.reshape(-1, h, w), tb.reshape(-1, h, w), data_range)
+    return rows.cpu().numpy(), int(h), int(w)
+
+
+def _psnr_of(se, voxels, data_range):
+    """10 log10(L^2 / MSE) with MSE = se / voxels; ``inf`` when the squared error is exactly 0."""
+    if se == 0:
+        return float("inf")
+    return float(10.0 * np.log10(float(data_range) ** 2 / (se / voxels)))
+
+
+def ssim(a, b, data_range):
+    """Structural similarity of one image or volume on the GPU: the mean over the slices of each slice's mean SSIM over its
+    window centres (the pixels at least 5 from every edge).  NumPy arrays or float32 device tensors -> Python float."""
+    rows, h, w = _similarity_sums(a, b, data_range, "ssim")
+    return float(np.mean(rows[:, 0] / float((h - 10) * (w - 10))))
+
+
+def psnr(a, b, data_range):
+    """Peak signal-to-noise ratio of one image or volume on the GPU: 10 log10(L^2 / MSE), MSE over all its voxels (fp64 sums of
+    fp64 differences); ``inf`` for identical inputs."""
+    rows, h, w = _similarity_sums(a, b, data_range, "psnr")
+    return _psnr_of(rows[:, 1].sum(), rows.shape[0] * h * w, data_range)
+
+
+def mae(a, b):
+    """Mean absolute error of one image or volume on the GPU (fp64 sums of fp64 differences)."""
+    rows, h, w = _similarity_sums(a, b, 1.0, "mae")
+    return float(rows[:, 2].sum() / (rows.shape[0] * h * w))
+
+
+TRANSLATION_TABLES = ("cycle", "paired")
+
+
+def translation_tables(rows, names, cells, shapes, data_range=1.0):
+    """The translation tables from per-slice sums.  ``rows``: float array [M, 3] = {sum of SSIM over window centres, SE, AE} per
+    compared slice (``ops.image_similarity``); ``names``: its slice names 'm_pid_z'; ``cells``: per slice ``(row, col, table)``
+    with table in ``TRANSLATION_TABLES``; ``shapes``: per slice ``(H, W)``.  Returns ``{table: (ssim, psnr, mae)}``, each an
+    [n_modal, n_modal] fp64 array.  A slice belongs to the volume 'm_pid' of its name; within a cell
+      volume SSIM = mean of its slices' SSIM (a slice's = its sum / ((H-10)(W-10))),
+      volume PSNR = 10 log10(L^2 / (sum SE / voxels)), ``inf`` when sum SE == 0 (from the volume's MSE, not a mean of slice PSNRs),
+      volume MAE  = sum AE / voxels,
+    and the cell is the mean over its volumes (as ``get_mo_matrix`` averages a modality's volumes); a cell without data is NaN.
+    Pure host code."""
+    rows = np.asarray(rows, dtype=np.float64).reshape(-1, 3)
+    names, cells, shapes = list(names), list(cells), list(shapes)
+    if not (len(names) == len(cells) == len(shapes) == rows.shape[0]):
+        raise ValueError(f"translation_tables: {rows.shape[0]} rows for {len(names)} names, {len(cells)} cells, {len(shapes)} shapes")
+    vols = OrderedDict()                                 # (table, row, col, 'm_pid') -> [sum of slice SSIM, slices, SE, AE, voxels]
+    for r, nm, (i, j, table), (h, w) in zip(rows, names, cells, shapes):
+        if table not in TRANSLATION_TABLES or not (0 <= i < cfg.n_modal and 0 <= j < cfg.n_modal):
+            raise ValueError(f"translation_tables: no cell {(i, j, table)!r}")
+        m, pid, _ = nm.split("_")
+        v = vols.setdefault((table, int(i), int(j), f"{m}_{pid}"), [0.0, 0, 0.0, 0.0, 0])
+        v[0] += r[0] / float((h - 10) * (w - 10)); v[1] += 1
+        v[2] += r[1]; v[3] += r[2]; v[4] += h * w
+    sums = {t: np.zeros((3, cfg.n_modal, cfg.n_modal)) for t in TRANSLATION_TABLES}
+    count = {t: np.zeros((cfg.n_modal, cfg.n_modal)) for t in TRANSLATION_TABLES}
+    for (table, i, j, _), (s, n, se, ae, voxels) in vols.items():
+        sums[table][0, i, j] += s / n
+        sums[table][1, i, j] += _psnr_of(se, voxels, data_range)
+        sums[table][2, i, j] += ae / voxels
+        count[table][i, j] += 1
+    out = {}
+    for t in TRANSLATION_TABLES:
+        with np.errstate(invalid="ignore", divide="ignore"):
+            out[t] = tuple(np.where(count[t] > 0, sums[t][k] / count[t], np.nan) for k in range(3))
+    return out
+
+
+def translation_text(tables):
+    """Six ``matrix_text`` blocks with an empty line between them: cycle SSIM, cycle PSNR, cycle MAE, paired SSIM, paired PSNR,
+    paired MAE ('%.4f' values separated by ','; ``nan`` / ``inf`` as Python formats them)."""
+    return "\n".join(matrix_text(m) for t in TRANSLATION_TABLES for m in tables[t])
+
+
+class TranslationMeter:
+    """The translation metrics of one test pass, kept on the device.  ``update`` compares a batch of image pairs with one
+    ``ops.image_similarity`` launch and keeps its [N, 3] rows there, with the slices' names and the cell ``(row, col, table)``
+    they count for; ``result`` makes the one stacked device-to-host copy and returns ``translation_tables`` of it.  Nothing waits
+    for the device before ``result``."""
+
+    def __init__(self, data_range=1.0):
+        self.data_range = float(data_range)
+        self._rows, self._names, self._cells, self._shapes = [], [], [], []
+
+    def update(self, a, b, names, row, col, table):
+        """Compare ``a`` with ``b`` (fp32 [N, H, W] or [N, 1, H, W] on the device); ``names``: N slice names 'm_pid_z'."""
+        from .. import ops
+        names = list(names)
+        if table not in TRANSLATION_TABLES or not (0 <= int(row) < cfg.n_modal and 0 <= int(col) < cfg.n_modal):
+            raise ValueError(f"TranslationMeter: no cell {(row, col, table)!r}")
+        if len(names) != a.shape[0]:
+            raise ValueError(f"TranslationMeter: {len(names)} names for {a.shape[0]} slices")
+        for nm in names:
+            if len(nm.split("_")) != 3:
+                raise ValueError(f"TranslationMeter: slice name {nm!r} is not 'm_pid_z'")
+        self._rows.append(ops.image_similarity(a, b, self.data_range))
+        self._names += names
+        self._cells += [(int(row), int(col), table)] * len(names)
+        self._shapes += [(int(a.shape[-2]), int(a.shape[-1]))] * len(names)
+
+    def rows(self):
+        """Everything collected so far as one float64 host array [M, 3]: one stacked copy."""
+        import torch
+        if not self._rows:
+            return np.zeros((0, 3))
+        return torch.cat(self._rows).cpu().numpy()
+
+    def result(self):
+        return translation_tables(self.rows(), self._names, self._cells, self._shapes, self.data_range)
 
 
 class Meter:

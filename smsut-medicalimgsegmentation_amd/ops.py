@@ -2638,3 +2638,45 @@ def surface_hd(pred_u8, gt_u8, n_cls, q=95.0, spacing=None):
     out = torch.empty(int(n_cls), 6, dtype=torch.float64, device=pred.device)
     H.call("smsut_surface_hd", pred, gt, out, ws, d, h, w, int(n_cls), planar, float(q) / 100.0, _s())
     return out.cpu().numpy()
+
+
+SIM_MIN_SIDE, SIM_MAX_SIDE, SIM_MAX_SLICES = 11, 4096, 65535      # the limits of smsut_image_similarity (include/smsut_hip.h)
+
+
+def image_similarity(a, b, data_range=1.0):
+    """Per slice of two image batches: float64 device tensor ``[N, 3]`` = {sum of SSIM over the slice's (H-10)(W-10) window
+    centres, SE = sum (a-b)^2 over all H W pixels, AE = sum |a-b|} (csrc/similarity.hip: 11x11 Gaussian window, sigma 1.5,
+    population moments, C1 = (0.01 L)^2, C2 = (0.03 L)^2 with L = ``data_range``; fixed-order fp64 sums, bitwise reproducible).
+    ``a``, ``b``: fp32 ``[N, H, W]`` or ``[N, 1, H, W]`` on the device, made contiguous here; 1 <= N <= 65535,
+    11 <= H, W <= 4096.  A shape or dtype mismatch, a size outside the limits or a ``data_range`` that is not finite and positive
+    raises ``ValueError`` before the device is touched.  Nothing is read back."""
+    for what, t in (("a", a), ("b", b)):
+        if not isinstance(t, torch.Tensor):
+            raise ValueError(f"image_similarity: {what} must be a tensor, got {type(t).__name__}")
+        if t.dtype != torch.float32:
+            raise ValueError(f"image_similarity: {what} must be float32, got {t.dtype}")
+    if a.shape != b.shape:
+        raise ValueError(f"image_similarity: shape mismatch {tuple(a.shape)} vs {tuple(b.shape)}")
+    if a.dim() == 4 and a.shape[1] == 1:
+        n, _, h, w = a.shape
+    elif a.dim() == 3:
+        n, h, w = a.shape
+    else:
+        raise ValueError(f"image_similarity: expected [N, H, W] or [N, 1, H, W], got {tuple(a.shape)}")
+    if not (1 <= n <= SIM_MAX_SLICES and SIM_MIN_SIDE <= h <= SIM_MAX_SIDE and SIM_MIN_SIDE <= w <= SIM_MAX_SIDE):
+        raise ValueError(f"image_similarity: needs 1..{SIM_MAX_SLICES} slices of {SIM_MIN_SIDE}..{SIM_MAX_SIDE} pixels a side, "
+                         f"got {(n, h, w)}")
+    try:
+        data_range = float(data_range)
+    except (TypeError, ValueError):
+        raise ValueError(f"image_similarity: data_range must be a number, got {data_range!r}") from None
+    if not (math.isfinite(data_range) and data_range > 0.0):
+        raise ValueError(f"image_similarity: data_range must be finite and positive, got {data_range}")
+    if a.device != b.device:
+        raise ValueError(f"image_similarity: a is on {a.device}, b on {b.device}")
+    a, b = a.detach().reshape(n, h, w).contiguous(), b.detach().reshape(n, h, w).contiguous()
+    H.ptr(a)                                                       # (a CPU tensor is refused here: no fallback)
+    ws = _byte_ws(H.call("smsut_image_similarity_ws", n, h, w), a)
+    out = torch.empty(n, 3, dtype=torch.float64, device=a.device)
+    H.call("smsut_image_similarity", a, b, out, ws, n, h, w, data_range, _s())
+    return out

@@ -74,3 +74,85 @@ class UGANShp0Trainer(BaseTrainer):
     def _forward_eval(self, img):
         seg, _ = self.net(img, val_phase=True)            # :267
         return seg
+
+    # ------------------------------------------------------------------ translation metrics of the test phase (cfg.test_translation)
+    def test(self, loader_type, expr_root):
+        """The base ``test``; with ``cfg.test_translation`` also ``translation_report`` over a fresh test loader."""
+        mo = super().test(loader_type, expr_root)
+        if cfg.test_translation:
+            _, _, loader = self.get_loaders(loader_type)
+            self.translation_report(loader, expr_root)
+        return mo
+
+    @staticmethod
+    def translation_partners():
+        """{modality id: the ids it is paired with} from ``cfg.test_translation_pairs``, both directions; a pair that names a
+        modality ``cfg.Modality`` does not have is skipped."""
+        names_of = cfg.Modality.__members__
+        partner = {}
+        for pa, pb in cfg.test_translation_pairs:
+            if pa in names_of and pb in names_of:
+                ia, ib = names_of[pa].value, names_of[pb].value
+                partner.setdefault(ia, []).append(ib)
+                partner.setdefault(ib, []).append(ia)
+        return partner
+
+    def translation_report(self, loader, expr_root):
+        """SSIM / PSNR / MAE of the unified translator over ``loader`` (batches ``(img, msk, modality ids, names 'm_pid_z')``), in
+        ``net.eval()`` under ``no_grad`` through the ``val_phase`` forward (netF is not involved); images are compared after
+        ``denorm`` (range [0, 1], data_range 1).  Two sets of [n_modal, n_modal] tables, row = source modality i, column = j:
+          cycle   denorm(x) against denorm(G(G(x, e_j - e_i), e_i - e_j)), the diagonal (zero vector both times) included;
+          paired  for each pair (a, b) of ``cfg.test_translation_pairs``, in both directions, denorm(G(x_a, e_b - e_a)) against
+                  denorm(x_b) for every slice 'a_pid_z' whose partner 'b_pid_z' is in the loader too (the real slices and the
+                  translations of the paired modalities are kept on the device, keyed by name); cells without data are NaN, a
+                  pair naming an unknown modality is skipped.
+        Writes ``{modality}_translation_matrix.csv`` -- cycle SSIM, PSNR, MAE, then paired SSIM, PSNR, MAE, '%.4f' rows separated
+        by ',' with an empty line between blocks -- logs it, and returns ``{table: (ssim, psnr, mae)}``.  Every comparison is one
+        ``ops.image_similarity`` launch whose rows stay on the device (``TranslationMeter``): nothing is read back before the
+        loader is exhausted, then one stacked copy."""
+        from ..misc.utils import TranslationMeter, maybe_mkdir, translation_text
+        self.net.eval()
+        meter = TranslationMeter(data_range=1.0)
+        partner = self.translation_partners()
+        real, translated = {}, []                          # name -> denorm(x) slice | (source name, target name, i, j, denorm(G(x)) slice)
+        with torch.no_grad():
+            for img, _, mdl, inm in loader:
+                x = img.to(self.device)
+                ids = [int(v) for v in mdl.tolist()]
+                inm = list(inm)[:len(ids)]
+                vec_org = self.label2onehot(mdl, cfg.n_modal).to(self.device)
+                x01 = self.denorm(x)
+                groups = {}                                # the batch's slices by source modality (one group with the in-turn loaders)
+                for k, i in enumerate(ids):
+                    groups.setdefault(i, []).append(k)
+                for k, i in enumerate(ids):
+                    if i in partner:
+                        real[inm[k]] = x01[k]
+                for j, vec in enumerate(self.create_vectors(vec_org, cfg.n_modal)):
+                    _, fwd = self.net(x, vec - vec_org, val_phase=True)
+                    _, back = self.net(fwd, vec_org - vec, val_phase=True)
+                    fwd01, back01 = self.denorm(fwd), self.denorm(back)
+                    for i, ks in groups.items():
+                        if len(ks) == len(ids):
+                            meter.update(x01, back01, inm, i, j, "cycle")
+                        else:
+                            sel = torch.tensor(ks, dtype=torch.int64).pin_memory().to(self.device, non_blocking=True)
+                            meter.update(x01.index_select(0, sel), back01.index_select(0, sel), [inm[k] for k in ks], i, j, "cycle")
+                        if j in partner.get(i, ()):
+                            for k in ks:
+                                m, pid, z = inm[k].split("_")
+                                translated.append((inm[k], f"{cfg.Modality(j).name}_{pid}_{z}", i, j, fwd01[k]))
+            by_cell = {}
+            for src, dst, i, j, t in translated:
+                if dst in real:
+                    by_cell.setdefault((i, j, tuple(t.shape)), []).append((src, t, real[dst]))
+            for (i, j, _), items in by_cell.items():
+                meter.update(torch.stack([t for _, t, _ in items]), torch.stack([r for _, _, r in items]),
+                             [src for src, _, _ in items], i, j, "paired")
+        tables = meter.result()
+        log = translation_text(tables)
+        maybe_mkdir(expr_root)
+        with open(pjoin(expr_root, f"{self.modality}_translation_matrix.csv"), "w") as f:
+            f.write(log)
+        self.info(log)
+        return tables
