@@ -1399,6 +1399,8 @@ class BasicBlockFn(Function):
             s, ms, rs = _bb_shortcut(p, x, x2, ws, st)
         out, pooled, ctx.pool_idx = _bb_tail(p, y2, m2, r2, g2, b2, s if p.has_sc else x, ms, rs, gs, bs, st)
         ctx.pair_w = leaves if p.pair else None      # the leaves a parked set's gradient goes to if it never meets a partner
+        # (pool: an output that brought no gradient reaches the backward as None, not as an NCHW tensor of zeros to convert and route)
+        ctx.set_materialize_grads(False)
         # ONE layout for the virtual-cat, conv-shortcut and identity forms: what a form lacks is None (identity: s is x itself)
         ctx.save_for_backward(x, x2, w1, w2, ws, y1, a1, y2, s, out, m1, r1, m2, r2, ms, rs, g1, b1, g2,
                               *((gs, b2, bs) if p.has_sc else (None, None, None)))

@@ -350,7 +350,8 @@ def test_fused_in_statistics_match_standalone_pass(ops, n, h, ci, co, k):
                                        (8, 128, 8, 16)])      # the first block after the stem: 8-channel tap-paired kernels
 def test_fused_basic_block_vs_torch(ops, n, h, ci, co):
     """The fused BasicBlock (forward + hand-written backward) against torch autograd of the reference
-    composition (network/blocks.py:53-80), incl. the identity-shortcut form and ragged tiles."""
+    composition (network/blocks.py:53-80), incl. the identity-shortcut form and ragged tiles.  The tight anchor of the block is
+    tests/test_block_fp64_gpu.py: fp64, inputs without sign flips, max-norm bars of a few 1e-6 on every branch of the plan."""
     if not ops.FUSED_BLOCK:
         pytest.skip("SMSUT_FUSED_BLOCK=0 in the environment")
     slope = 0.01
