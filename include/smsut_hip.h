@@ -714,6 +714,45 @@ int64_t smsut_image_similarity_ws(int n, int h, int w);
 int smsut_image_similarity(const float* a, const float* b, double* out, void* workspace, int n, int h, int w, double data_range,
                            void* stream);
 
+/* Volume preparation (csrc/volume.hip): raw scanner volume -> the processed grid the package trains and tests on.  Arrays are dense
+ * [D][H][W] = [z][y][x]; every axis 1 .. 4096, at most 2^31 - 1 voxels; otherwise SMSUT_EINVAL (the `_ws` queries: -1) and nothing
+ * is launched.  Nothing reads back to the host; every kernel runs on `stream`.
+ *
+ * Index map, shared by both resamplers: output index i of an axis reads the source at the continuous index
+ *   x = ((i + start) * num) / den - offset      (fp64: an exact integer product, one division, one subtraction)
+ * and the point is inside iff -0.5 <= x < n - 0.5 on every axis (n = the source's length); outside points are written as 0.
+ * num, den in 1 .. 4096; start, offset in 0 .. 4096.
+ *
+ * smsut_bspline_coefficients: the cubic B-spline interpolation coefficients of vol under whole-sample mirror boundaries (index
+ *   -1 -> 1, n -> n - 2) on every axis: per axis the solution of A c = v, A[i][mirror(i + k)] += (1/6, 4/6, 1/6), k = -1, 0, 1; an
+ *   axis of length 1 is copied.  Computed as the symmetric FIR h[k] = -6 z / (1 - z^2) z^|k|, z = sqrt(3) - 2, |k| <= 15, over the
+ *   mirrored line, each output one fixed-order fp64 sum rounded once to fp32 per axis.  out must not alias vol.
+ *   workspace: smsut_bspline_ws(d, h, w) bytes (one intermediate volume).
+ * smsut_resample_volume: out[od][oh][ow] = the cubic B-spline with coefficients coef[sd][sh][sw] at the mapped points: four weights
+ *   per axis on the mirror-folded indices floor(x) - 1 .. floor(x) + 2, fp64 accumulation in the order z (y (x)), rounded once.
+ * smsut_resample_labels: nearest neighbour, source index floor(x + 0.5) (halves round up); lut: 256 bytes applied to the SOURCE
+ *   value, or null.
+ *   workspace of both: smsut_resample_ws(od, oh, ow) bytes (the per-axis index / weight tables). */
+int64_t smsut_bspline_ws(int d, int h, int w);
+int smsut_bspline_coefficients(const float* vol, float* out, void* workspace, int d, int h, int w, void* stream);
+int64_t smsut_resample_ws(int od, int oh, int ow);
+int smsut_resample_volume(const float* coef, float* out, void* workspace, int sd, int sh, int sw, int od, int oh, int ow, int num_z,
+                          int num_y, int num_x, int den_z, int den_y, int den_x, int start_z, int start_y, int start_x, int off_z,
+                          int off_y, int off_x, void* stream);
+int smsut_resample_labels(const uint8_t* lab, uint8_t* out, void* workspace, const uint8_t* lut /*nullable*/, int sd, int sh, int sw,
+                          int od, int oh, int ow, int num_z, int num_y, int num_x, int den_z, int den_y, int den_x, int start_z,
+                          int start_y, int start_x, int off_z, int off_y, int off_x, void* stream);
+/* Exact order statistics: out[k] = the value at sorted rank r_k (0-based, ascending) of the n FINITE floats v, k < nr, 1 <= nr <= 8,
+ * 0 <= r_k < n <= 2^31 - 1 (ranks past nr are ignored).  MSD radix select over order-preserving 32-bit keys (-0.0 sorts below
+ * +0.0), four 8-bit levels, integer atomics only: exact and independent of the order of arrival.  NaN / Inf: outside the contract.
+ * workspace: smsut_order_statistics_ws(n, nr) bytes, zeroed by the call. */
+int64_t smsut_order_statistics_ws(int64_t n, int nr);
+int smsut_order_statistics(const float* v, float* out, void* workspace, int64_t n, int nr, int64_t r0, int64_t r1, int64_t r2,
+                           int64_t r3, int64_t r4, int64_t r5, int64_t r6, int64_t r7, void* stream);
+/* out[i] = (uint8)((min(max(v[i], lo), hi) - lo) / (hi - lo) * 255.0f), (lo, hi) = bounds[0..1] read on the device; fp32 in this
+ * order with IEEE division, converted by truncation; all zeros when hi == lo.  1 <= n <= 2^31 - 1. */
+int smsut_window_u8(const float* v, const float* bounds, uint8_t* out, int64_t n, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -2682,3 +2682,130 @@ def image_similarity(a, b, data_range=1.0):
     out = torch.empty(n, 3, dtype=torch.float64, device=a.device)
     H.call("smsut_image_similarity", a, b, out, ws, n, h, w, data_range, _s())
     return out
+
+
+# ------------------------------------------------------------------------------------------- volume preparation (csrc/volume.hip)
+VOL_MAX_DIM, VOL_MAX_VOXELS, ORDER_MAX_RANKS = 4096, 2 ** 31 - 1, 8      # the limits of the volume entry points (include/smsut_hip.h)
+
+
+def _vol_size(what, size):
+    try:
+        size = tuple(int(v) for v in size)
+    except (TypeError, ValueError):
+        raise ValueError(f"{what}: expected three integers (z, y, x), got {size!r}") from None
+    if len(size) != 3 or not all(1 <= v <= VOL_MAX_DIM for v in size) or size[0] * size[1] * size[2] > VOL_MAX_VOXELS:
+        raise ValueError(f"{what}: needs three axes of 1..{VOL_MAX_DIM} and at most 2^31 - 1 voxels, got {size}")
+    return size
+
+
+def _vol_tensor(what, t, dtype):
+    if not isinstance(t, torch.Tensor):
+        raise ValueError(f"{what}: expected a tensor, got {type(t).__name__}")
+    if t.dtype != dtype or t.dim() != 3:
+        raise ValueError(f"{what}: expected a {dtype} [D, H, W] tensor, got {t.dtype} {tuple(t.shape)}")
+    _vol_size(what, t.shape)
+    return t.detach().contiguous()
+
+
+def _axis_ints(what, name, v, lo):
+    try:
+        v = tuple(int(k) for k in v)
+    except (TypeError, ValueError):
+        raise ValueError(f"{what}: {name} must be three integers (z, y, x), got {v!r}") from None
+    if len(v) != 3 or not all(lo <= k <= VOL_MAX_DIM for k in v):
+        raise ValueError(f"{what}: {name} must be three integers in {lo}..{VOL_MAX_DIM}, got {v}")
+    return v
+
+
+def _resample_args(what, out_size, num, den, start, offset):
+    return (_vol_size(what + " out_size", out_size), _axis_ints(what, "num", num, 1), _axis_ints(what, "den", den, 1),
+            _axis_ints(what, "start", start, 0), _axis_ints(what, "offset", offset, 0))
+
+
+def bspline_coefficients(vol):
+    """The cubic B-spline interpolation coefficients of ``vol`` (fp32 ``[D, H, W]`` on the device) with whole-sample mirror
+    boundaries on every axis (index -1 -> 1, n -> n - 2; an axis of length 1 is copied): ITK's BSplineDecompositionImageFilter,
+    scipy's ``spline_filter(order=3, mode='mirror')``.  A new fp32 tensor of the same shape; nothing is read back."""
+    vol = _vol_tensor("bspline_coefficients", vol, torch.float32)
+    H.ptr(vol)
+    d, h, w = vol.shape
+    ws = _byte_ws(H.call("smsut_bspline_ws", d, h, w), vol)
+    out = torch.empty_like(vol)
+    H.call("smsut_bspline_coefficients", vol, out, ws, d, h, w, _s())
+    return out
+
+
+def resample_volume(coeff, out_size, num, den, start, offset=(0, 0, 0)):
+    """Evaluate the cubic B-spline with coefficients ``coeff`` (fp32 ``[D, H, W]``, from ``bspline_coefficients``) on the window
+    ``out_size = (oz, oy, ox)``: output index i of an axis reads the continuous index ``x = ((i + start) * num) / den - offset``
+    (fp64), and a point with ``x < -0.5`` or ``x >= n - 0.5`` on any axis is 0.  ``num``, ``den``, ``start``, ``offset``: three
+    integers each, ordered (z, y, x).  Only the window is written; returns fp32 ``[oz, oy, ox]``."""
+    coeff = _vol_tensor("resample_volume", coeff, torch.float32)
+    out_size, num, den, start, offset = _resample_args("resample_volume", out_size, num, den, start, offset)
+    H.ptr(coeff)
+    ws = _byte_ws(H.call("smsut_resample_ws", *out_size), coeff)
+    out = torch.empty(out_size, dtype=torch.float32, device=coeff.device)
+    H.call("smsut_resample_volume", coeff, out, ws, *coeff.shape, *out_size, *num, *den, *start, *offset, _s())
+    return out
+
+
+def resample_labels(lab_u8, out_size, num, den, start, offset=(0, 0, 0), lut=None):
+    """Nearest-neighbour resampling of a uint8 label volume ``[D, H, W]`` by ``resample_volume``'s index map: source index
+    ``floor(x + 0.5)`` (halves round up), 0 outside.  ``lut``: an optional 256-entry uint8 device tensor applied to the SOURCE value
+    (a grey-range -> class remap in the same pass).  Returns uint8 ``[oz, oy, ox]``."""
+    lab = _vol_tensor("resample_labels", lab_u8, torch.uint8)
+    out_size, num, den, start, offset = _resample_args("resample_labels", out_size, num, den, start, offset)
+    if lut is not None:
+        if not isinstance(lut, torch.Tensor) or lut.dtype != torch.uint8 or lut.numel() != 256:
+            raise ValueError("resample_labels: lut must be a uint8 tensor of 256 entries")
+        if lut.device != lab.device:
+            raise ValueError(f"resample_labels: lab is on {lab.device}, lut on {lut.device}")
+        lut = lut.contiguous()
+    H.ptr(lab)
+    ws = _byte_ws(H.call("smsut_resample_ws", *out_size), lab)
+    out = torch.empty(out_size, dtype=torch.uint8, device=lab.device)
+    H.call("smsut_resample_labels", lab, out, ws, lut, *lab.shape, *out_size, *num, *den, *start, *offset, _s())
+    return out
+
+
+def order_statistics(vol, ranks):
+    """The values ``np.partition`` would leave at the sorted positions ``ranks`` (1..8 integers in ``[0, n)``) of the ``n`` values of
+    the fp32 device tensor ``vol`` (any shape): an fp32 device tensor ``[len(ranks)]``, exact (an MSD radix select over
+    order-preserving integer keys; -0.0 and +0.0 compare equal as floats).  Every value must be FINITE: NaN and Inf are outside the
+    contract.  Nothing is read back."""
+    if not isinstance(vol, torch.Tensor) or vol.dtype != torch.float32:
+        raise ValueError("order_statistics: expected a float32 tensor")
+    n = vol.numel()
+    try:
+        ranks = [int(r) for r in ranks]
+    except (TypeError, ValueError):
+        raise ValueError(f"order_statistics: ranks must be integers, got {ranks!r}") from None
+    if not 1 <= n <= VOL_MAX_VOXELS:
+        raise ValueError(f"order_statistics: needs 1..2^31 - 1 values, got {n}")
+    if not 1 <= len(ranks) <= ORDER_MAX_RANKS or not all(0 <= r < n for r in ranks):
+        raise ValueError(f"order_statistics: needs 1..{ORDER_MAX_RANKS} ranks in [0, {n}), got {ranks}")
+    v = vol.detach().contiguous()
+    H.ptr(v)
+    ws = _byte_ws(H.call("smsut_order_statistics_ws", n, len(ranks)), v)
+    out = torch.empty(len(ranks), dtype=torch.float32, device=v.device)
+    H.call("smsut_order_statistics", v, out, ws, n, len(ranks), *(ranks + [0] * (ORDER_MAX_RANKS - len(ranks))), _s())
+    return out
+
+
+def window_u8(vol, bounds):
+    """``(uint8)((min(max(x, lo), hi) - lo) / (hi - lo) * 255.0f)`` of every value of the fp32 device tensor ``vol``, with
+    ``(lo, hi) = bounds``, a 2-float device tensor read on the device: fp32 in this order, IEEE division, truncation; all zeros when
+    ``hi == lo``.  Returns a uint8 tensor of ``vol``'s shape."""
+    if not isinstance(vol, torch.Tensor) or vol.dtype != torch.float32:
+        raise ValueError("window_u8: expected a float32 tensor")
+    if not isinstance(bounds, torch.Tensor) or bounds.dtype != torch.float32 or bounds.numel() != 2:
+        raise ValueError("window_u8: bounds must be a float32 tensor (lo, hi)")
+    if not 1 <= vol.numel() <= VOL_MAX_VOXELS:
+        raise ValueError(f"window_u8: needs 1..2^31 - 1 values, got {vol.numel()}")
+    if bounds.device != vol.device:
+        raise ValueError(f"window_u8: vol is on {vol.device}, bounds on {bounds.device}")
+    v, b = vol.detach().contiguous(), bounds.detach().contiguous()
+    H.ptr(v)
+    out = torch.empty(v.shape, dtype=torch.uint8, device=v.device)
+    H.call("smsut_window_u8", v, b, out, v.numel(), _s())
+    return out
