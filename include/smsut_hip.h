@@ -753,6 +753,33 @@ int smsut_order_statistics(const float* v, float* out, void* workspace, int64_t 
  * order with IEEE division, converted by truncation; all zeros when hi == lo.  1 <= n <= 2^31 - 1. */
 int smsut_window_u8(const float* v, const float* bounds, uint8_t* out, int64_t n, void* stream);
 
+/* ---------------------------------------------------------------------------------------------- test-time augmentation
+ * Inference with flipped / rotated copies of a slice and with ensembles (csrc/tta.hip; predict.py).  The reference has no inference
+ * entry point: this replaces the flip / rot90 / softmax / stack / mean / max chain an inference script would build from torch.
+ * Transform g = r + 4 f, r in 0..3, f in 0..1, on the last two axes of a slice x [H][W]:
+ *   F_g(x) = torch.rot90(f ? torch.flip(x, [-1]) : x, k = r, dims = (-2, -1));  odd r needs H == W.
+ * `transforms` (T ints in 0..7) and `members` (T device pointers) are HOST arrays, read before the call returns.
+ *
+ * smsut_tta_expand: img uint8 [N][H][W] -> out fp32 [T][N][1][H][W]; member t = F_{g_t}(slice), converted as the loader converts a
+ *   slice on the device (data_loader/inTurnLoader.py:166,173: `.float().div_(255.0).sub_(0.5).div_(0.5)`, where torch divides a
+ *   device tensor by a host scalar as a product with the scalar's reciprocal): ((float)u * (float)(1.0 / 255.0) - 0.5f) * 2.0f,
+ *   in fp32, each of the three steps rounded on its own, in this order -- bitwise what that torch expression gives.
+ * smsut_tta_merge: members[t]: logits fp32 [N][H][W][C] (NHWC) of the network run on member t of smsut_tta_expand (repeats of a
+ *   g are allowed: several networks), 4-byte aligned, read in place, each logit once.  Classes = channels 0 .. K-1.  Per output
+ *   pixel q, member by member in list order, all in fp32: p = the position of q in F_{g_t}; m = max_k z[p][k];
+ *   e_k = expf(z[p][k] - m); s = e_0 + e_1 + ... in channel order; acc_k += e_k / s.  Then mean_k = acc_k / (float)T;
+ *   pred uint8 [N][H][W] = the first maximum of mean_k by smsut_argmax_channels' comparison (the first maximum wins, a NaN wins);
+ *   conf (nullable) fp32 [N][H][W] = mean_pred; prob (nullable) fp32 [N][H][W][K] = mean_k.  No atomics, no cross-thread sums:
+ *   bitwise reproducible.
+ * Limits (otherwise SMSUT_EINVAL and nothing is launched; N == 0 returns SMSUT_OK without a launch): */
+#define SMSUT_TTA_MAX_MEMBERS 16   /* 1 <= T <= 16 */
+#define SMSUT_TTA_MAX_CLASSES 32   /* 1 <= K <= min(C, 32) */
+#define SMSUT_TTA_MAX_SLICES 65535 /* N <= 65535 */
+#define SMSUT_TTA_MAX_DIM 16384    /* 1 <= H, W <= 16384 */
+int smsut_tta_expand(const uint8_t* img, float* out, const int* transforms, int T, int N, int H, int W, void* stream);
+int smsut_tta_merge(const float* const* members, const int* transforms, uint8_t* pred, float* conf /*nullable*/,
+                    float* prob /*nullable*/, int T, int N, int H, int W, int C, int K, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

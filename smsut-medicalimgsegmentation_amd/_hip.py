@@ -252,6 +252,9 @@ SIGNATURES: Dict[str, str] = {
     "smsut_order_statistics_ws": "l i",
     "smsut_order_statistics": "ppp l i llllllll s",
     "smsut_window_u8": "ppp l s",
+    # tta.hip (inference: test-time augmentation and ensembling)
+    "smsut_tta_expand": "ppp iiii s",
+    "smsut_tta_merge": "ppppp iiiiii s",
 }
 _RET_I64 = {"smsut_wino_image_floats", "smsut_conv2d_wgrad_pair_ws", "smsut_convT2x2_wgrad_ps_ws", "smsut_conv2d_wgrad_sc_ws", "smsut_conv2d_k4_wgrad_ws", "smsut_conv2d_wgrad_f16_ws", "smsut_conv2d_wgrad_sc_f16_ws", "smsut_absmax_scale_ws", "smsut_conv2d_wgrad_generic_ws", "smsut_colsum_ws", "smsut_dicece_ws", "smsut_sum_ws",
             "smsut_conv2d_wgrad_mfma_ws", "smsut_convT2x2_wgrad_mfma_ws", "smsut_conv2d_flat_wgrad_ws", "smsut_conv1x1_wgrad_ws",

@@ -2809,3 +2809,126 @@ def window_u8(vol, bounds):
     out = torch.empty(v.shape, dtype=torch.uint8, device=v.device)
     H.call("smsut_window_u8", v, b, out, v.numel(), _s())
     return out
+
+
+# ------------------------------------------------------------------------------------------- test-time augmentation (csrc/tta.hip)
+# Transform g = r + 4 f (r in 0..3 quarter turns, f in 0..1) acts on the last two axes of a slice:
+#   F_g(x) = torch.rot90(torch.flip(x, [-1]) if f else x, k=r, dims=(-2, -1)),   F_g^-1(y) = flip_if_f(torch.rot90(y, k=-r, dims=(-2, -1)))
+# Odd r needs H == W.  The kernels, tests/tta_ref.py and predict.py all use this one definition.
+TTA_MAX_MEMBERS, TTA_MAX_CLASSES, TTA_MAX_SLICES, TTA_MAX_DIM = 16, 32, 65535, 16384     # the limits of smsut_tta_* (include/smsut_hip.h)
+TTA_SETS = {"none": (0,), "flips": (0, 4, 6, 2), "d4": (0, 1, 2, 3, 4, 5, 6, 7)}          # flips: identity, left-right, up-down, both
+
+
+def tta_transforms(name_or_list):
+    """A named transform set (``'none'``, ``'flips'``, ``'d4'``) or a sequence of integers ``g = r + 4 f`` in 0..7 (repeats allowed:
+    one entry per ensemble member) as a tuple of ints.  Pure host code; ``ValueError`` for an unknown name, an empty or over-long
+    list or an entry outside 0..7, ``TypeError`` for anything that is neither a name nor a sequence of integers."""
+    if isinstance(name_or_list, str):
+        if name_or_list not in TTA_SETS:
+            raise ValueError(f"tta_transforms: unknown set {name_or_list!r}; expected one of {sorted(TTA_SETS)}")
+        return TTA_SETS[name_or_list]
+    try:
+        items = list(name_or_list)
+    except TypeError:
+        raise TypeError(f"tta_transforms: expected a set name or a sequence of integers, got {type(name_or_list).__name__}") from None
+    for g in items:
+        if isinstance(g, bool) or not isinstance(g, int):
+            raise TypeError(f"tta_transforms: entries must be integers, got {g!r}")
+    if not 1 <= len(items) <= TTA_MAX_MEMBERS:
+        raise ValueError(f"tta_transforms: needs 1..{TTA_MAX_MEMBERS} transforms, got {len(items)}")
+    if not all(0 <= g <= 7 for g in items):
+        raise ValueError(f"tta_transforms: entries must lie in 0..7 (g = r + 4 f), got {items}")
+    return tuple(items)
+
+
+def _tta_check_plane(what, transforms, h, w):
+    if not (1 <= h <= TTA_MAX_DIM and 1 <= w <= TTA_MAX_DIM):
+        raise ValueError(f"{what}: H and W must lie in 1..{TTA_MAX_DIM}, got {(h, w)}")
+    if h != w and any(g & 1 for g in transforms):
+        raise ValueError(f"{what}: a quarter turn (odd r, transforms {[g for g in transforms if g & 1]}) needs a square slice, got {h} x {w}")
+
+
+def _tta_host_ints(values):
+    import ctypes
+    arr = (ctypes.c_int * len(values))(*values)
+    return arr, ctypes.addressof(arr)
+
+
+def tta_expand(img_u8, transforms):
+    """The augmented network inputs of a group of slices in one launch: ``img_u8`` uint8 ``[N, H, W]`` on the device ->
+    fp32 ``[T, N, 1, H, W]``; member ``t`` is ``F_g`` of every slice for ``g = transforms[t]``, converted exactly as the loader
+    converts a PNG slice on the device (bitwise ``u8.float().div(255).sub(.5).div(.5)`` of a device tensor).  ``TypeError`` for wrong types or devices, ``ValueError`` for
+    shapes, values or a quarter turn of a non-square slice, before the device is touched.  No CPU fallback."""
+    tr = tta_transforms(transforms)
+    if not isinstance(img_u8, torch.Tensor):
+        raise TypeError(f"tta_expand: img_u8 must be a tensor, got {type(img_u8).__name__}")
+    if img_u8.dtype != torch.uint8:
+        raise TypeError(f"tta_expand: img_u8 must be uint8, got {img_u8.dtype}")
+    if not img_u8.is_cuda:
+        raise TypeError(f"tta_expand: img_u8 must be on a HIP device, got {img_u8.device} (no CPU fallback)")
+    if img_u8.dim() != 3:
+        raise ValueError(f"tta_expand: expected [N, H, W] slices, got shape {tuple(img_u8.shape)}")
+    n, h, w = img_u8.shape
+    _tta_check_plane("tta_expand", tr, h, w)
+    if n > TTA_MAX_SLICES:
+        raise ValueError(f"tta_expand: at most {TTA_MAX_SLICES} slices, got {n}")
+    out = torch.empty(len(tr), n, 1, h, w, dtype=torch.float32, device=img_u8.device)
+    if n == 0:
+        return out
+    keep, addr = _tta_host_ints(tr)
+    H.call("smsut_tta_expand", img_u8.contiguous(), out, addr, len(tr), n, h, w, _s())
+    del keep                                                   # (the entry point has copied the list into the kernel arguments)
+    return out
+
+
+def tta_merge(members, transforms, classes=None, want_conf=False, want_prob=False):
+    """Test-time augmentation / ensembling in one pass (csrc/tta.hip).  ``members``: T logit tensors, logical NCHW ``[N, C, H, W]``
+    fp32 in the NHWC memory the networks leave them in (read in place, each logit once; they are not stacked), member ``t`` being
+    a network's output on ``tta_expand(...)[t]``; ``transforms``: their T transforms (a set name or integers, repeats allowed:
+    two networks x four flips is T = 8).  The softmax of channels ``0 .. classes-1`` of every member (``classes`` defaults to C;
+    CoraNet passes L + 1: head 0) is averaged on the un-transformed grid.  Returns ``(pred, conf, prob)``: ``pred`` uint8
+    ``[N, H, W]``, the first maximum of the mean by ``argmax_channels``' rule; ``conf`` fp32 ``[N, H, W]``, the mean probability
+    of that class, or None; ``prob`` fp32 ``[N, H, W, classes]`` or None.  Bitwise reproducible.  ``TypeError`` for wrong types
+    or devices, ``ValueError`` for shapes, values or a quarter turn of a non-square slice, before the device is touched."""
+    import ctypes
+    tr = tta_transforms(transforms)
+    try:
+        members = list(members)
+    except TypeError:
+        raise TypeError(f"tta_merge: members must be a sequence of tensors, got {type(members).__name__}") from None
+    for i, m in enumerate(members):
+        if not isinstance(m, torch.Tensor):
+            raise TypeError(f"tta_merge: member {i} must be a tensor, got {type(m).__name__}")
+        if m.dtype != torch.float32:
+            raise TypeError(f"tta_merge: member {i} must be float32, got {m.dtype}")
+    if not 1 <= len(members) <= TTA_MAX_MEMBERS:
+        raise ValueError(f"tta_merge: needs 1..{TTA_MAX_MEMBERS} members, got {len(members)}")
+    for i, m in enumerate(members):
+        if not m.is_cuda or m.device != members[0].device:
+            raise TypeError(f"tta_merge: member {i} must be on the first member's HIP device, got {m.device} (no CPU fallback)")
+    if len(tr) != len(members):
+        raise ValueError(f"tta_merge: {len(members)} members but {len(tr)} transforms")
+    if members[0].dim() != 4:
+        raise ValueError(f"tta_merge: expected NCHW logits, got shape {tuple(members[0].shape)}")
+    n, c, h, w = members[0].shape
+    for i, m in enumerate(members):
+        if tuple(m.shape) != (n, c, h, w):
+            raise ValueError(f"tta_merge: member {i} has shape {tuple(m.shape)}, member 0 {(n, c, h, w)}")
+    k = c if classes is None else int(classes)
+    if not 1 <= k <= min(c, TTA_MAX_CLASSES):
+        raise ValueError(f"tta_merge: classes must lie in 1..min(C, {TTA_MAX_CLASSES}), got {k} with C = {c}")
+    _tta_check_plane("tta_merge", tr, h, w)
+    if n > TTA_MAX_SLICES:
+        raise ValueError(f"tta_merge: at most {TTA_MAX_SLICES} slices, got {n}")
+    dev = members[0].device
+    pred = torch.empty(n, h, w, dtype=torch.uint8, device=dev)
+    conf = torch.empty(n, h, w, dtype=torch.float32, device=dev) if want_conf else None
+    prob = torch.empty(n, h, w, k, dtype=torch.float32, device=dev) if want_prob else None
+    if n == 0:
+        return pred, conf, prob
+    zs = [nhwc(m.detach()) for m in members]                  # (a network's output already is NHWC: no copy)
+    ptrs = (ctypes.c_void_p * len(zs))(*[z.data_ptr() for z in zs])
+    keep, addr = _tta_host_ints(tr)
+    H.call("smsut_tta_merge", ctypes.addressof(ptrs), addr, pred, conf, prob, len(zs), n, h, w, c, k, _s())
+    del keep, ptrs
+    return pred, conf, prob

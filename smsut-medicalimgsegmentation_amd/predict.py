@@ -1,0 +1,180 @@
+"""Inference: one raw scan in, one label volume out.
+
+    python -m smsut_amd.predict --trainer unet -i 000 --image scan.npy --spacing 5.0 1.5 1.5 --modality ct --tta flips --out out/
+
+``Predictor`` runs a trained network (or an ensemble) over uint8 slices of the processed grid, with optional test-time augmentation:
+the network sees the flipped / rotated copies of every slice (``ops.tta_expand``), and the class probabilities of all copies and all
+networks are averaged on the un-transformed grid in one pass (``ops.tta_merge``, csrc/tta.hip).  ``predict_volume`` wraps it between
+``prepare_volume`` (raw scanner array -> processed grid) and ``restore_labels`` (labels back on the scanner's grid), with the test
+phase's 3-D connected-component cleanup in between.  Everything stays on the device; reading DICOM / NIfTI is the caller's business
+(``.npy`` in and out).  The reference has no inference entry point: its only path through a trained network is the test phase, which
+needs a PNG tree, a split yaml and ground truth (trainer/baseTrainer.py:254-318).
+"""
+import argparse
+import os
+import types
+from typing import NamedTuple, Optional
+
+import numpy as np
+import torch
+
+from . import config as cfg
+from . import ops
+from .data_pprocess.volume import CROP_SIZE, NEW_SPACING, ResamplePlan, prepare_volume, restore_labels
+
+
+def group_plan(depth, batch_size):
+    """How ``depth`` slices are cut into groups of ``batch_size``: a list of ``(start, count, padding)`` with ``count + padding ==
+    batch_size``; only the last group is padded.  Pure host code."""
+    depth, batch_size = int(depth), int(batch_size)
+    if depth < 1 or batch_size < 1:
+        raise ValueError(f"group_plan: needs at least one slice and a batch of at least one, got {depth} slices, batch {batch_size}")
+    return [(s, min(batch_size, depth - s), batch_size - min(batch_size, depth - s)) for s in range(0, depth, batch_size)]
+
+
+def _modules_of(forward):
+    """The ``nn.Module`` s behind a forward callable, as far as they can be found: the callable itself, or, for a bound method of a
+    trainer, its ``net`` / ``net2`` / ``ema``."""
+    if isinstance(forward, torch.nn.Module):
+        return [forward]
+    owner = getattr(forward, "__self__", None)
+    if isinstance(owner, torch.nn.Module):
+        return [owner]
+    return [m for m in (getattr(owner, a, None) for a in ("net", "net2", "ema")) if isinstance(m, torch.nn.Module)]
+
+
+class Predictor:
+    """``forward``: one callable ``img [B, 1, H, W] -> logits [B, C, H, W]`` (a trainer's ``_forward_eval``, a module) or a list of
+    them (an ensemble: crossPse's two networks, mean-teacher's student and teacher).  ``tta``: a set name (``'none'``, ``'flips'``,
+    ``'d4'``) or a list of transforms (``ops.tta_transforms``).  ``classes``: the leading channels that are classes (default: all;
+    CoraNet: L + 1, head 0 of its 3L+1 channels).
+
+    Slices are processed in groups of ``batch_size``: one ``tta_expand`` launch, one forward of ``batch_size`` images per (network,
+    transform), one ``tta_merge`` launch.  The last group is padded with zero images to ``batch_size`` (as ``validate_epoch`` pads
+    it: captured graphs are per shape) and the padding is dropped.  Working memory is one group's members, not the volume's; nothing
+    is read back.  With one member and no confidence the prediction is ``ops.argmax_channels``' and the merge kernel does not run."""
+
+    def __init__(self, forward, batch_size=None, tta="none", classes=None):
+        self.forwards = list(forward) if isinstance(forward, (list, tuple)) else [forward]
+        if not self.forwards or not all(callable(f) for f in self.forwards):
+            raise TypeError("Predictor: forward must be a callable or a non-empty list of callables")
+        self.batch_size = int(cfg.batch_size if batch_size is None else batch_size)
+        if self.batch_size < 1:
+            raise ValueError(f"Predictor: batch_size must be at least 1, got {batch_size}")
+        self.transforms = ops.tta_transforms(tta)
+        self.classes = None if classes is None else int(classes)
+        self.members = len(self.forwards) * len(self.transforms)
+        if self.members > ops.TTA_MAX_MEMBERS:
+            raise ValueError(f"Predictor: {len(self.forwards)} networks x {len(self.transforms)} transforms = {self.members} members, "
+                             f"at most {ops.TTA_MAX_MEMBERS}")
+
+    def plan(self, depth):
+        return group_plan(depth, self.batch_size)
+
+    def predict_slices(self, image_u8, confidence=False):
+        """``image_u8``: uint8 ``[D, H, W]`` on the device, the processed grid.  Returns ``(pred, conf)``: uint8 ``[D, H, W]`` and,
+        with ``confidence``, the mean probability of the predicted class as fp32 ``[D, H, W]`` (else None), both on the device."""
+        if not isinstance(image_u8, torch.Tensor) or image_u8.dtype != torch.uint8:
+            raise TypeError("predict_slices: image_u8 must be a uint8 tensor")
+        if not image_u8.is_cuda:
+            raise TypeError(f"predict_slices: image_u8 must be on a HIP device, got {image_u8.device} (no CPU fallback)")
+        if image_u8.dim() != 3 or image_u8.shape[0] < 1:
+            raise ValueError(f"predict_slices: expected [D >= 1, H, W] slices, got shape {tuple(image_u8.shape)}")
+        d, h, w = image_u8.shape
+        ops._tta_check_plane("predict_slices", self.transforms, h, w)
+        image_u8 = image_u8.contiguous()
+        for f in self.forwards:
+            for m in _modules_of(f):
+                m.eval()
+        bs, tr = self.batch_size, self.transforms
+        pred = torch.empty(d, h, w, dtype=torch.uint8, device=image_u8.device)
+        conf = torch.empty(d, h, w, dtype=torch.float32, device=image_u8.device) if confidence else None
+        with torch.no_grad():
+            for start, count, padding in self.plan(d):
+                x = ops.tta_expand(image_u8[start:start + count], tr)              # [T, count, 1, H, W]
+                if padding:
+                    full = torch.zeros(len(tr), bs, 1, h, w, dtype=torch.float32, device=x.device)
+                    full[:, :count] = x
+                    x = full
+                outs = [f(x[t])[:count] for f in self.forwards for t in range(len(tr))]
+                k = outs[0].shape[1] if self.classes is None else self.classes
+                if len(outs) == 1 and not confidence and k == outs[0].shape[1]:
+                    pred[start:start + count] = ops.argmax_channels(outs[0])
+                else:
+                    p, c, _ = ops.tta_merge(outs, tr * len(self.forwards), classes=k, want_conf=confidence)
+                    pred[start:start + count] = p
+                    if confidence:
+                        conf[start:start + count] = c
+        return pred, conf
+
+
+class PredictResult(NamedTuple):
+    labels: torch.Tensor                       # uint8: on the scanner's grid when restored, else the processed grid
+    labels_processed: torch.Tensor             # uint8 [new_z, crop, crop]: the processed grid, after the cleanup
+    confidence: Optional[torch.Tensor]         # fp32, processed grid, or None
+    plan: ResamplePlan
+
+
+def predict_volume(predictor, image, spacing, modality, cleanup=True, restore=True, confidence=False, new_spacing=NEW_SPACING,
+                   crop_size=CROP_SIZE):
+    """Raw ``image`` ``[D, H, W]`` (NumPy array or device tensor, any real dtype) with voxel ``spacing`` ``(sz, sy, sx)`` ->
+    ``PredictResult``: ``prepare_volume`` -> ``predictor.predict_slices`` -> the test phase's 3-D 18-neighbour connected-component
+    cleanup (``cleanup``) -> ``restore_labels`` onto the input's grid (``restore``).  The confidence stays on the processed grid."""
+    image_u8, _, plan = prepare_volume(image, None, spacing, modality, new_spacing=new_spacing, crop_size=crop_size)
+    pred, conf = predictor.predict_slices(image_u8, confidence=confidence)
+    if cleanup:
+        pred = ops.cc_filter(pred, cfg.n_modal, per_slice=False)
+    labels = restore_labels(pred, plan, tuple(image.shape)) if restore else pred
+    return PredictResult(labels, pred, conf, plan)
+
+
+TRAINERS = {"unet": ("unetTrainer", "UnetTrainer"), "crossPse": ("crossPseTrainer", "crossPseTrainer"),
+            "meanTeacher": ("meanTeacherTrainer", "meanTeacherTrainer"), "coraNet": ("coraNetTrainer", "coraNetTrainer"),
+            "dtc": ("dtcTrainer", "dtcTrainer"), "ugan": ("uganTrainer", "UGANTrainer"),
+            "uganShp0": ("uganShp0Trainer", "UGANShp0Trainer"), "uganConsis": ("uganConsisTrainer", "UGANConsisTrainer")}
+
+
+def make_parser():
+    p = argparse.ArgumentParser(prog="python -m smsut_amd.predict", description="Segment one raw scan with a trained model.")
+    p.add_argument("--trainer", required=True, choices=sorted(TRAINERS), help="the method the model was trained with")
+    p.add_argument("-nm", "--expr_name", type=str, help="the run directory's name under config.expr_root (default: the trainer's class)")
+    p.add_argument("-i", "--model_id", type=str, required=True)
+    p.add_argument("-wh", "--which_ckpt", type=str, default="last")
+    p.add_argument("--image", required=True, help="the raw volume [D, H, W] as .npy")
+    p.add_argument("--spacing", type=float, nargs=3, required=True, metavar=("SZ", "SY", "SX"))
+    p.add_argument("--modality", required=True, help="'ct' windows to [-1000, 400]; any other name to the 0.05 / 99.5 percentiles")
+    p.add_argument("--tta", default="none", choices=sorted(ops.TTA_SETS))
+    p.add_argument("--confidence", action="store_true", help="also write confidence.npy (processed grid)")
+    p.add_argument("--batch_size", type=int, default=None)
+    p.add_argument("--out", required=True, help="directory for labels.npy, labels_processed.npy (and confidence.npy)")
+    return p
+
+
+def trainer_forwards(trainer):
+    """The eval forwards of a trainer built in its test phase and loaded with ``load_model``: its ``_forward_eval``.  A checkpoint
+    here holds ``net`` alone -- crossPse's ``net2`` and the teachers are never saved with it, as in the reference -- so the
+    command line has one network to wrap; an ensemble of separately loaded networks goes through ``Predictor([f1, f2], ...)``."""
+    return [trainer._forward_eval]
+
+
+def main(argv=None):
+    args = make_parser().parse_args(argv)
+    import importlib
+    mod, cls = TRAINERS[args.trainer]
+    trainer_cls = getattr(importlib.import_module(f"{__package__}.trainer.{mod}"), cls)
+    t = trainer_cls("test", types.SimpleNamespace(fold=0, expr_name=args.expr_name, model_id=args.model_id, write_env=False))
+    t.load_model(args.model_id, args.which_ckpt)
+    t.net.to(t.device)
+    predictor = Predictor(trainer_forwards(t), batch_size=args.batch_size, tta=args.tta, classes=cfg.n_label + 1)
+    image = np.load(args.image)
+    res = predict_volume(predictor, image, tuple(args.spacing), args.modality, confidence=args.confidence)
+    os.makedirs(args.out, exist_ok=True)
+    np.save(os.path.join(args.out, "labels.npy"), res.labels.cpu().numpy())
+    np.save(os.path.join(args.out, "labels_processed.npy"), res.labels_processed.cpu().numpy())
+    if args.confidence:
+        np.save(os.path.join(args.out, "confidence.npy"), res.confidence.cpu().numpy())
+    return res
+
+
+if __name__ == "__main__":
+    main()
