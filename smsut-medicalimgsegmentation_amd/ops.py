@@ -1158,6 +1158,7 @@ def _block_bwd_plan(p: BlockPlan, needs, mp, fin_available) -> BlockBwd:
     have run in another), asked at most once and only where a launch could use it."""
     n, h, w, ci, co = p[:5]
     f16a, f16, hs, has_sc, cat = p.f16a, p.f16, p.hs, p.has_sc, p.cat is not None
+    needs = tuple(needs) + (False,) * (14 - len(needs))  # (``basic_block`` passes no xa, xb, pool: their entries are missing, not False)
     chunks = H.call("smsut_in_chunks", n, h * w, co)
     # fp16 operands: the kernels that write gy2 / gs_t / gy1 hand their absolute maxima over (one slot per workgroup:
     # [gy2 | gs_t | gy1], nb each), the scales of the gradient operands come from those slots instead of a pass over each tensor

@@ -204,10 +204,12 @@ def make_inputs(c: Case):
     return t, grads, masks, info
 
 
-def step(c: Case, t, grads, masks, dtype, corrupt=None):
+def step(c: Case, t, grads, masks, dtype, corrupt=None, blk=None):
     """forward + backward of the restatement in ``dtype`` with the given masks (a missing one is filled in from the run's own
     pre-activation) -> {"out", "pooled", "pre1", "pre2", name: d / d name}.
-    ``corrupt``: one of the wrong blocks of the teeth test (CORRUPTIONS)."""
+    ``corrupt``: one of the wrong blocks of the teeth test (CORRUPTIONS).  ``blk``: a replay with ``block``'s signature that stands
+    in for it (tests/block_f16_ref.py: the fp16 rounding model)."""
+    blk = blk or block
     leaf = {k: v.detach().to(dtype).requires_grad_(True) for k, v in t.items()}            # (detach: never the shared inputs themselves)
     if corrupt == "act1_bit":                            # one mask bit flipped where the pre-activation is smallest
         masks = dict(masks)
@@ -219,7 +221,7 @@ def step(c: Case, t, grads, masks, dtype, corrupt=None):
         m.view(-1)[flat] = ~m.view(-1)[flat]
         masks["act1"] = m
     mid = {}
-    out, pooled = block(leaf, masks, c.slope, c.pool, mid, _inorm_dropped_row if corrupt == "stats2_row" else _inorm)
+    out, pooled = blk(leaf, masks, c.slope, c.pool, mid, _inorm_dropped_row if corrupt == "stats2_row" else _inorm)
     outs, gs = [out], [grads["gout"].to(dtype)]
     if c.pool:
         outs, gs = {"both": ([out, pooled], [gs[0], grads["gpooled"].to(dtype)]), "pooled": ([pooled], [grads["gpooled"].to(dtype)]),
@@ -284,16 +286,17 @@ def rows_of(c: Case, got, ref: Ref, names):
     return [(k, got[k], ref.r64[k], ref.r32[k], kind_of(k, c)) for k in names]
 
 
-def compare(tag, rows):
+def compare(tag, rows, col="d32"):
     """rows: (name, tensor under test, fp64, fp32 replay, kind).  Prints err / d32 / bar of every tensor; -> [(name, err, bar)] of
-    those that miss bar = max(4 d32, FLOORS[kind]), on max |got - fp64| / max |fp64|.  ``worst``: the largest err / bar."""
+    those that miss bar = max(4 d32, FLOORS[kind]), on max |got - fp64| / max |fp64|.  ``col``: what the yardstick column is
+    called in the print ("d16" when it holds the fp16 rounding model of tests/block_f16_ref.py)."""
     fails = []
     for name, got, r64, r32, kind in rows:
         assert tuple(got.shape) == tuple(r64.shape), (tag, name, tuple(got.shape), tuple(r64.shape))
         d32 = rel_err(r32.numpy(), r64.numpy())
         bar = max(4.0 * d32, FLOORS[kind])
         e = rel_err(got.detach().cpu().numpy(), r64.numpy())
-        print(f"{tag} {name}: err {e:.3g}  d32 {d32:.3g}  bar {bar:.3g} ({kind})  err/bar {e / bar:.3f}")
+        print(f"{tag} {name}: err {e:.3g}  {col} {d32:.3g}  bar {bar:.3g} ({kind})  err/bar {e / bar:.3f}")
         if not e < bar:
             fails.append((name, e, bar))
     return fails
@@ -328,41 +331,68 @@ def like_shape(c: Case):
 
 
 def expected_launches(H, p, b, pooled_only=False):
-    """entry points of one forward + backward, in order, read from ops._bb_* (fp32 operands, outside a wino_prepared scope).
+    """entry points of one forward + backward, in order, read from ops._bb_* (outside a wino_prepared scope; fp32 operands, and the
+    fp16 plans of tests/block_f16_ref.py: their `_f16` / `_hs` twins and the launches that make the scales of the gradient operands).
     H: the library's host queries (_hip).  pooled_only: a pool block whose skip output brought no gradient (the plain pooling backward
     makes the tail's upstream gradient first)."""
     n, h, w, ci, co = p[:5]
-    f = ["smsut_conv2d_fwd_mfma_stats" + ("_sc_fin" if p.fin else "_sc" if p.fused_sc else "_cat" if p.virtual else "")]
+    a16, c16 = "_f16" if p.f16a else "", "_f16" if p.f16 else ""
+    if p.hs:
+        f = ["smsut_conv2d_fwd_mfma_stats_sc_f16_hs"]
+    else:
+        f = ["smsut_conv2d_fwd_mfma_stats" + ("_sc_fin" if p.fin else "_sc" + a16 if p.fused_sc else "_cat" + a16 if p.virtual else a16)]
     if p.fin:
         f += ["smsut_conv2d_fwd_mfma_stats_inaff_fin"]
     else:
-        f += ["smsut_in_finalize_fwd", "smsut_conv2d_fwd_mfma_stats_inaff"] if p.inaff else ["smsut_instnorm_fwd_partials", "smsut_conv2d_fwd_mfma_stats"]
+        if p.inaff:
+            f += ["smsut_in_finalize_fwd", "smsut_conv2d_fwd_mfma_stats_inaff"]
+        elif p.hs:
+            f += ["smsut_in_finalize_fwd", "smsut_conv2d_fwd_mfma_stats_inaff_f16_hsx"]
+        else:
+            f += ["smsut_instnorm_fwd_partials", "smsut_conv2d_fwd_mfma_stats" + c16]
         f += ["smsut_in_finalize_fwd2" if p.fused_sc else "smsut_in_finalize_fwd"]
     if p.has_sc and not p.fused_sc:
         streaming = H.call("smsut_conv1x1_supported", ci, co) and H.call("smsut_conv1x1_tiles", n, h * w, co) > 0
         f += ["smsut_conv1x1_fwd_cat" if p.virtual else "smsut_conv1x1_fwd" if streaming else "smsut_conv2d_fwd_mfma_stats", "smsut_in_finalize_fwd"]
-    f += ["smsut_restail_fwd_pool" if p.pool else "smsut_restail_fwd"]
+    f += ["smsut_restail_fwd_pool" if p.pool else "smsut_restail_fwd_hs" if p.hs else "smsut_restail_fwd"]
     g = ["smsut_maxpool2_bwd"] if pooled_only else []
-    g += [{"pool": "smsut_restail_bwd_pool", "fin": "smsut_restail_bwd_fin", "plain": "smsut_restail_bwd"}[b.tail]]
+    g += [{"pool": "smsut_restail_bwd_pool", "hs": "smsut_restail_bwd_hs", "amax": "smsut_restail_bwd_amax", "fin": "smsut_restail_bwd_fin",
+           "plain": "smsut_restail_bwd"}[b.tail]]
+    if p.f16:                                            # the scale of gy2: from the tail's maxima, else a pass over the tensor
+        g += ["smsut_absmax_finish" if b.nb else "smsut_absmax_scale"]
     if not b.pers2:
-        g += ["smsut_conv2d_fwd_mfma", "smsut_instnorm_bwd"]
+        g += ["smsut_conv2d_fwd_mfma" + c16, "smsut_instnorm_bwd"]
     else:
-        g += ["smsut_conv2d_dgrad_mfma_bwdstats_fin"] if b.fin_b else ["smsut_conv2d_dgrad_mfma_bwdstats", "smsut_in_finalize_bwd"]
-        g += ["smsut_in_apply_bwd"]
-    g += ["smsut_conv2d_wgrad_mfma_inaff" if p.inaff else "smsut_conv2d_wgrad_mfma"]
-    if b.fused_wsc:
+        if p.f16:
+            g += ["smsut_conv2d_dgrad_mfma_bwdstats_f16" + ("_hs" if p.hs else "")]
+        else:
+            g += ["smsut_conv2d_dgrad_mfma_bwdstats_fin" if b.fin_b else "smsut_conv2d_dgrad_mfma_bwdstats"]
+        g += [] if b.fin_b else ["smsut_in_finalize_bwd"]
+        g += ["smsut_in_apply_bwd_hs" if p.hs else "smsut_in_apply_bwd_amax" if b.amax1 else "smsut_in_apply_bwd"]
+    if p.hs or b.f16w2:
+        g += ["smsut_conv2d_wgrad_f16_xh_inaff" if p.hs else "smsut_conv2d_wgrad_f16"]
+    else:
+        g += ["smsut_conv2d_wgrad_mfma_inaff" if p.inaff else "smsut_conv2d_wgrad_mfma"]
+    if p.f16a:                                           # the scale of gy1, or ONE over [gy1 | gs_t] where a fused-shortcut gradient reads both
+        both = b.fused_wsc16 or b.fused_dsc16
+        g += ["smsut_absmax_finish" if b.amax1 else "smsut_absmax_scale2" if both else "smsut_absmax_scale"]
+    if b.fused_wsc16:
+        g += ["smsut_conv2d_wgrad_sc_f16"]
+    elif b.fused_wsc:
         g += ["smsut_conv2d_wgrad_mfma_sc"]
     else:
-        g += ["smsut_conv2d_wgrad_mfma_cat" if p.virtual else "smsut_conv2d_wgrad_mfma"]
+        g += ["smsut_conv2d_wgrad_f16" if b.f16w1 else "smsut_conv2d_wgrad_mfma_cat" if p.virtual else "smsut_conv2d_wgrad_mfma"]
         if p.has_sc:
             g += ["smsut_conv1x1_wgrad_cat" if p.virtual else "smsut_conv1x1_wgrad"]
-    if b.dx == "sc":
+    if b.dx == "sc_f16":
+        g += ["smsut_conv2d_dgrad_mfma_sc_f16"]
+    elif b.dx == "sc":
         g += ["smsut_conv2d_dgrad_mfma_sc"]
     elif b.dx == "split":
-        g += ["smsut_conv1x1_fwd_split", "smsut_conv2d_fwd_mfma_split"]
+        g += ["smsut_conv1x1_fwd_split", "smsut_conv2d_fwd_mfma_split" + a16]
     elif b.dx is not None:
         g += ["smsut_conv2d_fwd_mfma"] if b.dx == "accum_k1" else ["smsut_conv1x1_fwd"] if p.has_sc else []
-        g += ["smsut_conv2d_fwd_mfma"] + (["smsut_concat2"] if p.cat is not None else [])
+        g += ["smsut_conv2d_fwd_mfma" + a16] + (["smsut_concat2"] if p.cat is not None else [])
     return f, g
 
 
