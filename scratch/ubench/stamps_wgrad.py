@@ -1,3 +1,5 @@
+"""Wave timeline of the tap-split weight gradient (diagnostic build of conv_mfma_wgrad.hip with -DSMSUT_STAMPS, which has its own
+stamp buffer and setter: smsut_dbg_wgrad_stamps)."""
 import ctypes, sys, numpy as np, torch
 lib = ctypes.CDLL('scratch/ubench/libconv_stamps.so')
 B, h, ci, co = 16, 64, 64, 64
@@ -13,7 +15,7 @@ def run():
     assert rc == 0, rc
 for _ in range(3): run()
 torch.cuda.synchronize()
-assert lib.smsut_dbg_set_stamps(P(st), 0) == 0
+assert lib.smsut_dbg_wgrad_stamps(P(st), 0) == 0
 run(); torch.cuda.synchronize()
 s = st.cpu().numpy().reshape(512, 4, 16).astype(np.int64)
 s = s[s[:, 0, 0] > 0]

@@ -36,11 +36,12 @@ SIGNATURES: Dict[str, str] = {
     "smsut_restail_bwd_fin": "pppppppppppp pp ppp pppp pp iii f s",
     "smsut_restail_bwd_amax": "pppppppppppp pp ppp pppp pp iii f s",
     "smsut_in_apply_bwd_amax": "pppppppp pp p iii s",
+    "smsut_absmax_scale_ws": "l",
+    "smsut_absmax_scale": "p l pp s",
+    "smsut_absmax_scale2": "p l p l pp s",
     "smsut_absmax_finish": "p i p s",
     "smsut_amax_blocks": "iii",
     "smsut_instnorm_bwd": "pppppp ppppp p iii f s",
-    "smsut_sgd_momentum_multi": "ppp i fff s",
-    "smsut_sgd_chunk": "",
     "smsut_restail_fwd_pool": "pppppppppp ppp iiii f i s",
     "smsut_restail_bwd_pool": "ppp pppppppppp pp ppp pppp p pp iiii f i s",
     "smsut_instnorm_pool_fwd_partials": "ppppppp iiiii ff s",
@@ -53,7 +54,7 @@ SIGNATURES: Dict[str, str] = {
     "smsut_conv2d_wgrad_generic": "pppp iiiiiiiiiii s",
     "smsut_colsum_ws": "li",
     "smsut_colsum": "ppp li s",
-    # conv_mfma.hip
+    # conv_mfma.hip (forward / data-gradient: 3x3 and 1x1, ConvTranspose2x2, 4x4 s1 p1, fp16-operand forms)
     "smsut_conv2d_mfma_supported": "iiiii",
     "smsut_conv2d_fwd_mfma": "ppp iiiiii i s",
     "smsut_conv2d_fwd_mfma_pre": "ppp iiiiii i p s",
@@ -64,30 +65,11 @@ SIGNATURES: Dict[str, str] = {
     "smsut_conv2d_fwd_mfma_stats": "pppp iiiiii s",
     "smsut_conv2d_fwd_mfma_stats_pre": "pppp iiiiii p s",
     "smsut_conv2d_fwd_mfma_cfg": "ppp iiiiii ii s",
-    "smsut_wino_image_floats": "ii",
-    "smsut_wino_prepare": "ppppp i s",
-    "smsut_conv2d_wgrad_mfma_supported": "iiiii",
-    "smsut_conv2d_wgrad_mfma_ws": "iiiiii",
-    "smsut_conv2d_wgrad_mfma": "pppp iiiiii s",
     "smsut_convT2x2_mfma_supported": "ii",
     "smsut_convT2x2_fwd_mfma": "ppp iiiii s",
     "smsut_convT2x2_dgrad_mfma": "ppp iiiii s",
-    "smsut_convT2x2_wgrad_mfma_ws": "iiiii",
-    "smsut_convT2x2_wgrad_mfma": "pppp iiiii s",
-    "smsut_convT2x2_ps_supported": "ii",
-    "smsut_convT2x2_fwd_ps": "ppp iiiii s",
-    "smsut_convT2x2_wgrad_ps_ws": "iiiii",
-    "smsut_convT2x2_wgrad_ps": "pppp iiiii s",
-    # conv1x1.hip
-    "smsut_conv1x1_supported": "ii",
-    "smsut_conv1x1_tiles": "iii",
-    "smsut_conv1x1_fwd": "pppp iiii i s",
-    "smsut_conv1x1_wgrad_ws": "iiii",
-    "smsut_conv1x1_wgrad": "pppp iiii s",
     "smsut_conv2d_fwd_mfma_stats_inaff": "pppp pppp f iiiii s",
     "smsut_conv2d_fwd_mfma_stats_inaff_pre": "pppp pppp f iiiii p s",
-    "smsut_conv2d_wgrad_mfma_inaff": "pppp pppp f iiiii s",
-    "smsut_conv2d_wgrad_mfma_slabs": "ppp pppp f iiiii s",
     "smsut_conv2d_mfma_form": "iiiiii",
     "smsut_conv2d_mfma_cat_supported": "iiiii",
     "smsut_conv2d_fwd_mfma_stats_cat": "ppppp iiiii s",
@@ -99,23 +81,11 @@ SIGNATURES: Dict[str, str] = {
     "smsut_conv2d_fwd_mfma_stats_sc_pre": "pppppppp iiiii p s",
     "smsut_conv2d_dgrad_sc_supported": "iiiiii",
     "smsut_conv2d_dgrad_mfma_sc": "pppppp iiiiii s",
-    "smsut_conv2d_wgrad_sc_supported": "iiiii",
-    "smsut_conv2d_wgrad_sc_ws": "iiiii",
-    "smsut_conv2d_wgrad_mfma_sc": "pp i pppp iiiii s",
-    "smsut_conv2d_wgrad_mfma_cat": "pp i ppp iiiiii s",
     "smsut_conv2d_fwd_mfma_stats_sc_fin": "pppppppp ppppp f iiiii p s",
     "smsut_conv2d_fwd_mfma_stats_inaff_fin": "pppppppp f ppp f iiiii p s",
     "smsut_conv2d_dgrad_mfma_bwdstats_fin": "ppppppppp f ppp iiiii p s",
-    "smsut_conv2d_wgrad_pair_supported": "iiiiiiiii",
-    "smsut_conv2d_wgrad_pair_ws": "iiiiiiiii",
-    "smsut_conv2d_wgrad_pair": "pppppp i pppppp i i pp f pp iiii s",
-    "smsut_conv2d_wgrad_pair_slabs": "pppp i pppp i pp f p iiii s",
-    # 4x4 s1 p1 (networks.NLayerDiscriminator)
     "smsut_conv2d_k4_supported": "ii",
     "smsut_conv2d_k4_fwd": "ppp iiiii i s",
-    "smsut_conv2d_k4_wgrad_ws": "iiiii",
-    "smsut_conv2d_k4_wgrad": "pppp iiiii s",
-    # fp16-operand forms (config 5)
     "smsut_conv2d_f16_supported": "iii",
     "smsut_conv2d_fwd_mfma_f16": "pppp iiiiii i s",
     "smsut_conv2d_fwd_mfma_stats_f16": "pppp iiiiii s",
@@ -126,26 +96,54 @@ SIGNATURES: Dict[str, str] = {
     "smsut_conv2d_f16_hs_supported": "iiiiii",
     "smsut_conv2d_fwd_mfma_stats_f16_hs": "ppppp iiiii s",
     "smsut_conv2d_fwd_mfma_stats_f16_hsx": "pppp iiiii s",
-    "smsut_conv2d_wgrad_f16_xh": "ppppp iiiii s",
-    "smsut_conv2d_wgrad_f16_xh_inaff": "ppppp pppp f iiiii s",
     "smsut_conv2d_fwd_mfma_stats_inaff_f16_hsx": "pppp pppp f iiiii s",
     "smsut_conv2d_fwd_mfma_stats_sc_f16_hs": "pppppppp iiiii s",
-    "smsut_conv2d_wgrad_f16_supported": "iiiii",
-    "smsut_conv2d_wgrad_f16_ws": "iiiii",
-    "smsut_conv2d_wgrad_f16": "pp i pppp iiiii s",
-    "smsut_absmax_scale_ws": "l",
-    "smsut_absmax_scale": "p l pp s",
-    "smsut_absmax_scale2": "p l p l pp s",
     "smsut_conv2d_dgrad_sc_f16_supported": "iiiiii",
     "smsut_conv2d_dgrad_mfma_sc_f16": "ppppppp iiiiii s",
-    "smsut_conv2d_wgrad_sc_f16_supported": "iiiii",
-    "smsut_conv2d_wgrad_sc_f16_ws": "iiiii",
-    "smsut_conv2d_wgrad_sc_f16": "pp i ppppp iiiii s",
-    "smsut_conv1x1_fwd_cat": "pp i ppp iiii s",
-    "smsut_conv1x1_wgrad_cat": "pp i ppp iiii s",
     "smsut_conv2d_mfma_split_supported": "iiiiii",
     "smsut_conv2d_fwd_mfma_split": "pppp iiiiiii s",
     "smsut_conv2d_fwd_mfma_split_pre": "pppp iiiiiii p s",
+    # conv_mfma_wgrad.hip (LDS-staged weight gradient of the same convs; first rung: conv_wgrad_rr.hip)
+    "smsut_conv2d_wgrad_mfma_supported": "iiiii",
+    "smsut_conv2d_wgrad_mfma_ws": "iiiiii",
+    "smsut_conv2d_wgrad_mfma": "pppp iiiiii s",
+    "smsut_convT2x2_wgrad_mfma_ws": "iiiii",
+    "smsut_convT2x2_wgrad_mfma": "pppp iiiii s",
+    "smsut_conv2d_wgrad_mfma_inaff": "pppp pppp f iiiii s",
+    "smsut_conv2d_wgrad_mfma_slabs": "ppp pppp f iiiii s",
+    "smsut_conv2d_wgrad_sc_supported": "iiiii",
+    "smsut_conv2d_wgrad_sc_ws": "iiiii",
+    "smsut_conv2d_wgrad_mfma_sc": "pp i pppp iiiii s",
+    "smsut_conv2d_wgrad_mfma_cat": "pp i ppp iiiiii s",
+    "smsut_conv2d_wgrad_pair_supported": "iiiiiiiii",
+    "smsut_conv2d_wgrad_pair_ws": "iiiiiiiii",
+    "smsut_conv2d_wgrad_pair": "pppppp i pppppp i i pp f pp iiii s",
+    "smsut_conv2d_wgrad_pair_slabs": "pppp i pppp i pp f p iiii s",
+    "smsut_conv2d_k4_wgrad_ws": "iiiii",
+    "smsut_conv2d_k4_wgrad": "pppp iiiii s",
+    "smsut_conv2d_wgrad_f16_xh": "ppppp iiiii s",
+    "smsut_conv2d_wgrad_f16_xh_inaff": "ppppp pppp f iiiii s",
+    "smsut_conv2d_wgrad_f16_supported": "iiiii",
+    "smsut_conv2d_wgrad_f16_ws": "iiiii",
+    "smsut_conv2d_wgrad_f16": "pp i pppp iiiii s",
+    "smsut_conv2d_wgrad_sc_f16_supported": "iiiii",
+    "smsut_conv2d_wgrad_sc_f16_ws": "iiiii",
+    "smsut_conv2d_wgrad_sc_f16": "pp i ppppp iiiii s",
+    # conv_wino.hip
+    "smsut_wino_image_floats": "ii",
+    "smsut_wino_prepare": "ppppp i s",
+    # conv1x1.hip
+    "smsut_convT2x2_ps_supported": "ii",
+    "smsut_convT2x2_fwd_ps": "ppp iiiii s",
+    "smsut_convT2x2_wgrad_ps_ws": "iiiii",
+    "smsut_convT2x2_wgrad_ps": "pppp iiiii s",
+    "smsut_conv1x1_supported": "ii",
+    "smsut_conv1x1_tiles": "iii",
+    "smsut_conv1x1_fwd": "pppp iiii i s",
+    "smsut_conv1x1_wgrad_ws": "iiii",
+    "smsut_conv1x1_wgrad": "pppp iiii s",
+    "smsut_conv1x1_fwd_cat": "pp i ppp iiii s",
+    "smsut_conv1x1_wgrad_cat": "pp i ppp iiii s",
     "smsut_conv1x1_fwd_split": "pppp iiiiii s",
     "smsut_conv1x1_thin_supported": "ii",
     "smsut_conv1x1_thin_dgrad": "ppp iiii s",
@@ -183,6 +181,8 @@ SIGNATURES: Dict[str, str] = {
     "smsut_copy_channels": "p ii p ii i l s",
     "smsut_concat2": "p i p i p l i s",
     "smsut_modal_planes": "ppp i l ii s",
+    "smsut_sgd_momentum_multi": "ppp i fff s",
+    "smsut_sgd_chunk": "",
     # photometric.hip
     "smsut_photo_parts": "i",
     "smsut_photo_hist": "pp ii s",

@@ -190,7 +190,7 @@ struct ConvCall {
   int transposed_bits() const { return (transposed_w ? 1 : 0) | (accumulate ? 2 : 0); }
 };
 
-// ---- one description of a 3x3 / 1x1 weight-gradient launch (conv_mfma.hip, conv_wgrad_rr.hip) ---------------------------------------
+// ---- one description of a 3x3 / 1x1 weight-gradient launch (conv_mfma_wgrad.hip, conv_wgrad_rr.hip) ---------------------------------
 // gw [KS*KS (+ 1 with gs)][Cin][Cout] = sum_p x[p + tap] (x) gy[p]: every kernel writes one slab per split into `part`, sum_splits
 // adds them in a fixed order.  The shape and the forms are all that picks a kernel and its split count, so the planning queries
 // (`_supported`, `_ws`) ask with a WgradKey and no operand is made up for them.

@@ -1,4 +1,4 @@
-// Internal interface between conv_mfma.hip (entry points, form selection) and conv_wgrad_rr.hip (the register-row weight gradient).
+// Internal interface between conv_mfma_wgrad.hip (entry points, wgrad_select) and conv_wgrad_rr.hip (the register-row weight gradient).
 #pragma once
 #include "common.h"
 

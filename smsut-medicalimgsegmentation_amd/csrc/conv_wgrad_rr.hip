@@ -1,7 +1,7 @@
 // 3x3 weight gradient with REGISTER-RESIDENT ROWS (r04) -- reference op: the gradient of conv3x3 w.r.t. its weight inside
 // BasicBlock (/root/reference/network/blocks.py:10-12, :53-80), i.e. gw[tap][ci][co] = sum_p x[p + tap][ci] * gy[p][co].
 //
-// The LDS-staged kernels of conv_mfma.hip (conv_mfma_wgrad / conv_mfma_wgrad_ts) pay a per-tile skeleton -- two barriers and a
+// The LDS-staged kernels of conv_mfma_wgrad.hip (conv_mfma_wgrad / conv_mfma_wgrad_ts) pay a per-tile skeleton -- two barriers and a
 // register -> LDS publish per 8x16-pixel tile -- plus a prologue and a slab epilogue that every workgroup of the single resident
 // round runs at the same time; they sit at 50-70 % of the fp32 MFMA peak (profiles/r03_notes.md).  This kernel has NO LDS staging
 // and NO barrier in its main loop: with the pixels as the MFMA K dimension, lane (lm, kq) of v_mfma_f32_16x16x4_f32 needs ONE

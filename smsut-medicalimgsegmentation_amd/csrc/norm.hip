@@ -427,6 +427,39 @@ __device__ __forceinline__ void amax_emit(float m, float* slots) {
   __syncthreads();
 }
 
+// per-tensor power-of-two scale for an fp16 gradient operand: out2 = {s, 1/s}, s = 2^(14 - ceil(log2(max|x|))) so that the
+// largest element lands in [2^13, 2^14] (fp16 max is 65504; what underflows is < 2^-38 of the largest element).
+__global__ void __launch_bounds__(TPB) k_absmax_partial(const float* __restrict__ x, int64_t n, float* __restrict__ part) {
+  __shared__ float sm4[4];
+  float m = 0.f;
+  const int64_t n4 = n >> 2;
+  const float4* x4 = reinterpret_cast<const float4*>(x);
+  for (int64_t i = (int64_t)blockIdx.x * TPB + threadIdx.x; i < n4; i += (int64_t)gridDim.x * TPB) {
+    const float4 v = x4[i];
+    m = fmaxf(fmaxf(m, fmaxf(fabsf(v.x), fabsf(v.y))), fmaxf(fabsf(v.z), fabsf(v.w)));
+  }
+  if (blockIdx.x == 0 && threadIdx.x < (n & 3)) m = fmaxf(m, fabsf(x[(n4 << 2) + threadIdx.x]));
+  m = block_max_256(m, sm4);
+  if (threadIdx.x == 0) part[blockIdx.x] = m;
+}
+__global__ void __launch_bounds__(TPB) k_absmax_final(const float* __restrict__ part, int nparts, float* __restrict__ out2) {
+  __shared__ float sm4[4];
+  float m = 0.f;
+  for (int i = threadIdx.x; i < nparts; i += TPB) m = fmaxf(m, part[i]);
+  m = block_max_256(m, sm4);
+  if (threadIdx.x == 0) {
+    float s = 1.f;
+    if (m > 0.f && m < 3.0e38f) {
+      int e;
+      frexpf(m, &e);                          // m = f * 2^e, f in [0.5, 1)  ->  m <= 2^e
+      int k = 14 - e;
+      k = k > 120 ? 120 : (k < -120 ? -120 : k);
+      s = ldexpf(1.f, k);
+    }
+    out2[0] = s; out2[1] = 1.f / s;
+  }
+}
+
 template <int VEC, bool HS = false, bool AMAX = false, bool POOLG = false>   // AMAX: hand max|gx| over (amax non-null); compile-time, so
 __global__ void __launch_bounds__(TPB)                       // that the fp32 path's instantiation carries nothing of it.  POOLG: gy is the
 in_apply_bwd(                                                // gradient of the 2x2-average-pooled output (see in_moments_partial), pw = W
@@ -1292,6 +1325,41 @@ int smsut_in_apply_bwd(const float* gz, const float* x, const float* mean, const
   c.gy = gz; c.a_mean = a_mean; c.b_mean = b_mean; c.gx = gx; c.ggamma = ggamma; c.gbeta = gbeta;
   return run_in_bwd(c);
 }
+
+// ---- per-tensor abs-max scale {s, 1/s} of a gradient operand of the fp16-operand convolutions (k_absmax_partial / k_absmax_final)
+int64_t smsut_absmax_scale_ws(int64_t n) { (void)n; return 1024; }
+// out2 (device float[2]) = {s, 1/s}: the power-of-two scale that brings max|x| into [2^13, 2^14] (1 for an all-zero tensor)
+int smsut_absmax_scale(const float* x, int64_t n, float* out2, float* workspace, void* stream) {
+  SMSUT_REQUIRE(x && out2 && workspace && n > 0 && (reinterpret_cast<uintptr_t>(x) & 15) == 0);
+  hipStream_t st = (hipStream_t)stream;
+  int blocks = (int)cdiv64(n >> 2, TPB * 4);
+  blocks = blocks < 1 ? 1 : (blocks > 1024 ? 1024 : blocks);
+  k_absmax_partial<<<blocks, TPB, 0, st>>>(x, n, workspace);
+  k_absmax_final<<<1, TPB, 0, st>>>(workspace, blocks, out2);
+  SMSUT_LAUNCH_CHECK();
+  return SMSUT_OK;
+}
+
+// ... from maxima the producing kernels handed over (smsut_restail_bwd_amax / smsut_in_apply_bwd_amax): the scale of max(amax[0..n))
+int smsut_absmax_finish(const float* amax, int n, float* out2, void* stream) {
+  SMSUT_REQUIRE(amax && out2 && n > 0);
+  k_absmax_final<<<1, TPB, 0, (hipStream_t)stream>>>(amax, n, out2);
+  SMSUT_LAUNCH_CHECK();
+  return SMSUT_OK;
+}
+// ... of two tensors at once (one scale for both: the fused shortcut data-/weight-gradient reads [gy | gs] as one operand)
+int smsut_absmax_scale2(const float* x, int64_t n, const float* x2, int64_t n2, float* out2, float* workspace, void* stream) {
+  SMSUT_REQUIRE(x && x2 && out2 && workspace && n > 0 && n2 > 0 && ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(x2)) & 15) == 0);
+  hipStream_t st = (hipStream_t)stream;
+  auto nb = [](int64_t m) { const int b = (int)cdiv64(m >> 2, TPB * 4); return b < 1 ? 1 : (b > 512 ? 512 : b); };
+  const int b1 = nb(n), b2 = nb(n2);
+  k_absmax_partial<<<b1, TPB, 0, st>>>(x, n, workspace);
+  k_absmax_partial<<<b2, TPB, 0, st>>>(x2, n2, workspace + b1);
+  k_absmax_final<<<1, TPB, 0, st>>>(workspace, b1 + b2, out2);
+  SMSUT_LAUNCH_CHECK();
+  return SMSUT_OK;
+}
+
 // workgroups of the per-image apply kernels (= amax slots per output tensor of the _amax entry points)
 int smsut_amax_blocks(int N, int HW, int C) {
   if (N <= 0 || HW <= 0 || C <= 0) return 0;

@@ -25,18 +25,18 @@ TAPS = (0, 4, 7, 8, -1)      # one-hot single taps (a wrong tap pairing shows as
 
 # ================================================================================================ restated plans
 def fwd_p_eligible(n, h, w, k, m):
-    """conv_mfma.hip:2195-2198"""
+    """fwd_p_eligible (conv_mfma.hip)"""
     return (k in (8, 16, 32, 64) and w % 16 == 0 and h % 8 == 0 and m % 16 == 0 and n * (h // 8) * (w // 16) * (m // 16) >= 1024
             and n * h * w * max(k, m) < 2 ** 31)
 
 
 def f16_supported(ks, k, m):
-    """smsut_conv2d_f16_supported (conv_mfma.hip:3373-3375)"""
+    """smsut_conv2d_f16_supported (conv_mfma.hip)"""
     return ks in (1, 3) and k >= 16 and k % 16 == 0 and m >= 1
 
 
 def select_fwd_p_f16(h, k, m, split=0):
-    """select_fwd_p with fp16 operands (conv_mfma.hip:2242-2249; no Winograd form, no 8-channel form): (TH, NTN, NCH)"""
+    """select_fwd_p with fp16 operands (conv_mfma.hip; no Winograd form, no 8-channel form): (TH, NTN, NCH)"""
     if k == 16 and h % 16 == 0:
         return (16, 1, 1)
     if k == 32 and m % 32 == 0 and not (split and split % 32 != 0):
@@ -48,8 +48,8 @@ P_INSTANCES = ((16, 1, 1), (8, 1, 1), (8, 2, 2), (8, 1, 2), (8, 1, 4))       # e
 
 
 def per_tile_row_f16(n, h, w, m, transposed):
-    """dispatch_fwd<3> below the persistent kernel with fp16 operands (conv_mfma.hip:2281-2299; the 8-pixel-wide tile of :2291 asks
-    !f16): (row name, TH, NTN).  The tile is always 16 pixels wide."""
+    """dispatch_fwd<3> below the persistent kernel with fp16 operands (its launch_fwd rows, conv_mfma.hip; the 8-pixel-wide tile of the
+    8x8-plane row asks !f16): (row name, TH, NTN).  The tile is always 16 pixels wide."""
     nt, tx = cdiv(m, 16), cdiv(w, 16)
     wg16 = tx * cdiv(h, 16) * n * ((nt + 1) // 2)
     wg8 = tx * cdiv(h, 8) * n * ((nt + 1) // 2)
@@ -65,16 +65,16 @@ def per_tile_row_f16(n, h, w, m, transposed):
 
 
 ROWS_FWD = {"h4", "nt1", "wg16", "wg8", "fall"}          # rows of that table a forward fp16 call can reach
-ROWS_DGRAD = {"h4", "nt1", "wg16", "fall"}               # ("wg8" is forward-only, :2298)
+ROWS_DGRAD = {"h4", "nt1", "wg16", "fall"}               # ("wg8" is forward-only: its row of dispatch_fwd asks !c.transposed_w)
 
 
 def ckw_f16(ks, k, cat):
-    """channels per LDS pass of the per-tile kernel with fp16 operands (launch_fwd, conv_mfma.hip:1958-1966)"""
+    """channels per LDS pass of the per-tile kernel with fp16 operands (launch_fwd, conv_mfma.hip)"""
     return 32 if (ks == 3 and k % 32 == 0 and k >= 32 and (not cat or (k // 2) % 32 == 0)) else 16
 
 
 def plan_wgrad_f16(n, h, w, ci, co):
-    """plan_wgrad_f16 over plan_wgrad (conv_mfma.hip:3431-3436, 2653-2679): (cit, cot, splits, tiles_per_split, total tiles).  The
+    """plan_wgrad_f16 over plan_wgrad (conv_mfma_wgrad.hip): (cit, cot, splits, tiles_per_split, total tiles).  The
     split plan is the fp32 kernels' (slabs counted with their CIT = Cin > 16), only the slab shape is the fp16 kernel's own."""
     cit0, cot0 = (2 if ci > 16 else 1), (2 if co > 16 else 1)
     total = n * cdiv(w, 16) * cdiv(h, 8)
@@ -86,7 +86,7 @@ def plan_wgrad_f16(n, h, w, ci, co):
 
 
 def wgrad_f16_supported(n, h, w, ci, co):
-    """smsut_conv2d_wgrad_f16_supported (conv_mfma.hip:3427-3430)"""
+    """smsut_conv2d_wgrad_f16_supported = wgrad_f16_shape_ok (conv_mfma_wgrad.hip)"""
     return h % 8 == 0 and w % 16 == 0 and ci % 16 == 0 and co % 16 == 0 and n * h * w * max(ci, co) < 2 ** 31
 
 
@@ -173,13 +173,13 @@ def persistent_splits(ci):
 
 
 def walk_lengths(items, nz, cus):
-    """launch_fwd_p (conv_mfma.hip:2037-2045): ipw = ceil(items nz / (CUs occ)) for the occupancy of the launched instantiation, which has
+    """launch_fwd_p (conv_mfma.hip): ipw = ceil(items nz / (CUs occ)) for the occupancy of the launched instantiation, which has
     no query: every value 1..8"""
     return {cdiv(items * nz, cus * occ) for occ in range(1, WG_PER_CU + 1)}
 
 
 # ================================================================================================ 3. weight gradient
-# conv_f16_wgrad<CIT, COT, DUAL, SC, XH, INAFF> (launch_wgrad_f16, conv_mfma.hip:3442-3488): CIT = 2 iff Cin % 32 == 0, COT alike; DUAL
+# conv_f16_wgrad<CIT, COT, DUAL, SC, XH, INAFF> (launch_wgrad_f16, conv_mfma_wgrad.hip): CIT = 2 iff Cin % 32 == 0, COT alike; DUAL
 # = virtual cat, SC = fused shortcut (10 tap rows), XH = fp16 x, INAFF = raw fp16 y1 normalised while staged; grid (splits, Cin / 16 CIT,
 # Cout / 16 COT).  Forms: plain, cat, sc, sccat, xh, xhaff.
 # Columns: n, h, w, ci, co, forms, ca values of the cat forms, what the plane is.

@@ -282,7 +282,7 @@ def run_forms(H, n, h, w, ci, co, legs, prepared=False, splits=None, seed=3):
 def full_legs(ci, co):
     """every form the persistent kernels have for [ci -> co]: virtual cat needs two halves of whole 16-channel chunks (ci % 32 == 0),
     a split two parts of whole 16-channel tiles (ci >= 32), the fused-shortcut data-gradient co in {16, 32}
-    (smsut_conv2d_dgrad_sc_supported, conv_mfma.hip:2843-2849), the BST form a reduction width (co) the persistent kernels take"""
+    (smsut_conv2d_dgrad_sc_supported, conv_mfma.hip), the BST form a reduction width (co) the persistent kernels take"""
     legs = list(BASIC) + ["inaff"]
     if co in (16, 32, 64) or (co >= 64 and co % 16 == 0):
         legs.append("bst")
@@ -299,7 +299,7 @@ def full_legs(ci, co):
 
 
 def ipw_candidates(items, nz, cus):
-    """launch_fwd_p (conv_mfma.hip:2037-2045): ipw = ceil(items nz / (CUs occ)) for the occupancy occ of the launched instantiation,
+    """launch_fwd_p (conv_mfma.hip): ipw = ceil(items nz / (CUs occ)) for the occupancy occ of the launched instantiation,
     which has no query: every value 1..8 a CU can hold"""
     return {cdiv(items * nz, cus * occ) for occ in range(1, WG_PER_CU + 1)}
 
@@ -318,8 +318,8 @@ def is_prime(v):
 
 
 # ================================================================================================ 1. resident Winograd
-# dispatch_fwd<3> (conv_mfma.hip:2271-2275) sends a shape to select_fwd_p when fwd_p_eligible (:2195-2198: Kdim in {8, 16, 32, 64},
-# W % 16 == 0, H % 8 == 0, Ndim % 16 == 0, N (H / 8) (W / 16) (Ndim / 16) >= 1024); select_fwd_p (:2240-2241) takes the Winograd
+# dispatch_fwd<3> (conv_mfma.hip) sends a shape to select_fwd_p when fwd_p_eligible (Kdim in {8, 16, 32, 64},
+# W % 16 == 0, H % 8 == 0, Ndim % 16 == 0, N (H / 8) (W / 16) (Ndim / 16) >= 1024); select_fwd_p (its winograd_on() row) takes the Winograd
 # instantiation launch_fwd_p<3, 16, 1, NCH, false, false, true> for Kdim = 16 NCH in {16, 32} on H % 16 == 0: 16 x 16 items, NTN = 1
 # (nz = Ndim / 16).  units = N (H / 8) (W / 16) (Ndim / 16); items = N (H / 16) (W / 16).
 #   (2053,16,16,16->16)  items 2053 (prime), nz 1: a walk by 5 items over 8 CUs' worth; data-gradient the same kernel.  FULL.
@@ -372,7 +372,7 @@ def test_resident_winograd(H, cus, case):
 
 
 # ================================================================================================ 2. streamed Winograd
-# select_fwd_p (conv_mfma.hip:2222-2229) hands every fp32 form of a wino_l_shape (:2202-2204: Kdim >= 64 and smsut_wino_l_eligible,
+# select_fwd_p (conv_mfma.hip) hands every fp32 form of a wino_l_shape (Kdim >= 64 and smsut_wino_l_eligible,
 # conv_wino.hip:853-856: H % 16 == W % 16 == 0, Kdim % 16 == Ndim % 16 == 0) to smsut_wino_l_launch (conv_wino.hip:858-873):
 #   ntn = 2 when Ndim % 32 == 0 && !(y2 && split % 32 != 0) && items (Ndim / 32) >= CUs, else 1       (conv_wino.hip:867)
 #   nz = Ndim / (16 ntn), ipw = ceil(items nz / CUs), grid.x = ceil(items / ipw)                         (conv_wino.hip:786-792)
@@ -437,8 +437,8 @@ def test_streamed_winograd(H, cus, case, prepared):
 
 
 # ================================================================================================ 3. direct persistent forms
-# select_fwd_p (conv_mfma.hip:2230-2249) for the shapes the Winograd forms leave (H % 16 == 8, Kdim 8, Ndim 8, Kdim 64 off 16-row planes):
-#   Ndim 8 (data-gradient forms; dispatch_fwd :2276-2279 with fwd_p_n8_eligible :2255-2258: Kdim in {16, 32}, N (H / 8) (W / 16) >= 1024):
+# select_fwd_p (conv_mfma.hip) for the shapes the Winograd forms leave (H % 16 == 8, Kdim 8, Ndim 8, Kdim 64 off 16-row planes):
+#   Ndim 8 (data-gradient forms; dispatch_fwd<3> with fwd_p_n8_eligible: Kdim in {16, 32}, N (H / 8) (W / 16) >= 1024):
 #            Kdim 16 -> <3,16,1,1,N8> on H % 16 == 0 else <3,8,1,1,N8>; Kdim 32 -> <3,8,1,2,N8>
 #   Kdim 8  -> <3,16,1,1,K8> on H % 16 == 0 else <3,8,1,1,K8>
 #   Kdim 32, Ndim % 32 == 0, no split off 32 -> <3,8,2,2>;  Kdim 16 -> <3,8,1,1>;  Kdim 32 -> <3,8,1,2>;  Kdim 64 -> <3,8,1,4>
@@ -469,7 +469,7 @@ def test_direct_persistent_8row_items(H, cus, case):
 
 
 # Kdim 8 (forward, statistics, fused shortcut: K8) and Ndim 8 (data-gradient plain, accumulate, fused shortcut: N8); the fused-shortcut
-# data-gradient of [8 -> 16] reduces over 2 * 16 = 32 channels: <3,8,1,2,N8> with the shortcut's second half (:2082-2085)
+# data-gradient of [8 -> 16] reduces over 2 * 16 = 32 channels: <3,8,1,2,N8> with the shortcut's second half (launch_fwd_p, F_SC2 | F_N8)
 #   (260,16,32,8->16)  units 1040; K8 on 16-row items, N8 <3,16,1,1,N8>      (130,24,48,8->16)  units 1170; 8-row items both ways
 #   (260,16,32,8->32)  data-gradient Kdim 32 -> <3,8,1,2,N8>; no fused-shortcut data-gradient (co must be 16 for an 8-channel result)
 K8N8 = [(260, 16, 32, 8, 16, ("fwd", "stats", "sc", "dgrad", "acc", "dsc")), (130, 24, 48, 8, 16, ("fwd", "stats", "sc", "dgrad", "acc", "dsc")),
@@ -481,16 +481,16 @@ def test_direct_persistent_8_channels(H, case):
     n, h, w, ci, co, legs = case
     assert ci == 8
     assert H.call("smsut_conv2d_mfma_form", n, h, w, ci, co, 0) == 0 and H.call("smsut_conv2d_mfma_persistent", n, h, w, ci, co, 3, 0) == 1
-    th = 16 if h % 16 == 0 else 8                                                      # conv_mfma.hip:2235
+    th = 16 if h % 16 == 0 else 8                                                      # select_fwd_p: 16-row items when H % 16 == 0
     assert H.call("smsut_conv2d_mfma_tiles", n, h, w, ci, co, 3, 0) == (h // th) * (w // 16)
-    # the 8-channel result has no query (smsut_conv2d_mfma_persistent asks Ndim % 16 == 0): fwd_p_n8_eligible restated (:2255-2258)
+    # the 8-channel result has no query (smsut_conv2d_mfma_persistent asks Ndim % 16 == 0): fwd_p_n8_eligible restated
     assert co in (16, 32) and w % 16 == 0 and h % 8 == 0 and n * (h // 8) * (w // 16) >= 1024
     assert H.call("smsut_conv2d_mfma_form", n, h, w, co, ci, 0) == 0 and H.call("smsut_conv2d_mfma_form", n, h, w, 2 * co, ci, 1) == 0
     run_forms(H, n, h, w, ci, co, legs)
 
 
 def test_fused_shortcut_dgrad_at_64_channels_stays_direct(H):
-    """sc2_64 (conv_mfma.hip:2219-2222): on a shape whose every other form is a Winograd kernel, the fused-shortcut data-gradient with
+    """sc2_64 (select_fwd_p, conv_mfma.hip): on a shape whose every other form is a Winograd kernel, the fused-shortcut data-gradient with
     2 Cout = 64 reduction channels runs the direct <3,8,1,4> form -- both against fp64"""
     n, h, w, ci, co = 257, 16, 16, 64, 32
     assert H.call("smsut_conv2d_mfma_form", n, h, w, 2 * co, ci, 1) == 0            # the fused-shortcut data-gradient: direct
@@ -500,7 +500,7 @@ def test_fused_shortcut_dgrad_at_64_channels_stays_direct(H):
     run_forms(H, n, h, w, ci, co, ("fwd", "dgrad", "dsc", "dscsplit"), splits=(32, 16))
 
 
-# smsut_conv2d_fwd_mfma_cfg (conv_mfma.hip:2326-2339): the instantiations select_fwd_p can choose, at tiny shapes no 1024-unit rule
+# smsut_conv2d_fwd_mfma_cfg (dispatch_fwd_cfg, conv_mfma.hip): the instantiations select_fwd_p can choose, at tiny shapes no 1024-unit rule
 # guards -- 22 / 23 are the 16-row direct forms only SMSUT_WINOGRAD=0 selects.  cfg -> (TH, NTN, NCH); Kdim = 16 NCH, Ndim % (16 NTN) == 0.
 CFGS = {20: (8, 1, 1), 21: (8, 1, 2), 22: (16, 1, 1), 23: (16, 1, 2), 25: (8, 2, 2), 28: (8, 1, 4), 30: (16, 1, 1), 31: (16, 1, 2)}
 
@@ -529,8 +529,8 @@ def test_forced_persistent_instantiations(H, cfg):
 
 # ================================================================================================ 4. the per-tile kernel
 def tile_branch(N, Hh, W, ndim, transposed):
-    """dispatch_fwd<3> below the persistent kernels (conv_mfma.hip:2281-2299, isc = osc = G = ntap_out = 1, fp32): (TH, NTN, MW).  A
-    restatement -- only TH and MW show in smsut_conv2d_mfma_tiles; edit together with those lines."""
+    """dispatch_fwd<3> below the persistent kernels (its launch_fwd rows, conv_mfma.hip; isc = osc = G = ntap_out = 1, fp32): (TH, NTN, MW).  A
+    restatement -- only TH and MW show in smsut_conv2d_mfma_tiles; edit together with those rows."""
     nt, tx = cdiv(ndim, 16), cdiv(W, 16)
     wg16 = tx * cdiv(Hh, 16) * N * ((nt + 1) // 2)
     wg8 = tx * cdiv(Hh, 8) * N * ((nt + 1) // 2)
@@ -591,14 +591,14 @@ def test_per_tile_kernel(H, case):
 def test_per_tile_table_is_covered():
     fwd, dgr = {c[7][0] for c in PER_TILE}, {c[7][1] for c in PER_TILE if c[7][1]}
     assert fwd == {(4, 1, 16), (8, 1, 8), (8, 1, 16), (8, 2, 16), (16, 2, 16)}
-    assert dgr == {(4, 1, 16), (8, 1, 8), (8, 1, 16), (16, 2, 16)}                       # (<8,.,2> is forward-only, :2298)
+    assert dgr == {(4, 1, 16), (8, 1, 8), (8, 1, 16), (16, 2, 16)}                       # (<8,.,2> is forward-only: !c.transposed_w)
     assert {c[3] for c in PER_TILE} >= {4, 12, 20, 40, 64} and {c[4] for c in PER_TILE} >= {1, 5, 20, 48}
     assert {c[2] % 16 for c in PER_TILE} >= {1, 15} and any(c[2] < 16 for c in PER_TILE)
 
 
 # ================================================================================================ 5. LDS weight gradients
 def plan_wgrad(N, Hh, W, ci, co, rows=9):
-    """plan_wgrad (conv_mfma.hip:2653-2679): (cit, cot, splits, tiles_per_split, total tiles) on 8 x 16 pixel tiles"""
+    """plan_wgrad (conv_mfma_wgrad.hip): (cit, cot, splits, tiles_per_split, total tiles) on 8 x 16 pixel tiles"""
     cit, cot = (2 if ci > 16 else 1), (2 if co > 16 else 1)
     total = N * cdiv(W, 16) * cdiv(Hh, 8)
     slabs = cdiv(ci, 16 * cit) * cdiv(co, 16 * cot)
@@ -609,8 +609,8 @@ def plan_wgrad(N, Hh, W, ci, co, rows=9):
 
 
 def wgrad_kernel(N, Hh, W, ci, co, aff):
-    """wgrad_mfma_launch once the register-row kernel has declined (conv_mfma.hip:3196-3240)"""
-    if Hh * W <= 64 and W % 4 == 0 and ci % 32 == 0 and co % 32 == 0 and N * Hh * W <= 4096 and not aff:     # plane_wgrad_applies :3168-3171
+    """wgrad_select once the register-row kernel has declined (below_rr; conv_mfma_wgrad.hip)"""
+    if Hh * W <= 64 and W % 4 == 0 and ci % 32 == 0 and co % 32 == 0 and N * Hh * W <= 4096 and not aff:     # plane_wgrad_applies
         return "plane"
     cit, cot = (2 if ci > 16 else 1), (2 if co > 16 else 1)
     if cit == 2 and cot == 2 and Hh % 8 == 0 and W % 16 == 0 and ci % 32 == 0 and co % 32 == 0:
@@ -619,7 +619,7 @@ def wgrad_kernel(N, Hh, W, ci, co, aff):
 
 
 def sum_cols(wsize):
-    """launch_sum_splits (conv_mfma.hip:1935-1937)"""
+    """launch_sum_splits (conv_mfma_wgrad.hip)"""
     return 64 if wsize >= 32768 else (32 if wsize >= 8192 else 16)
 
 
@@ -695,7 +695,7 @@ def test_lds_wgrad_short_last_split(H, case):
     assert tps > 1 and total - (splits - 1) * tps == 1, "the last split must be short"
 
 
-# sum_splits<16 | 32 | 64> by wsize = 9 Cin Cout on each side of 8192 and 32768 (conv_mfma.hip:1935-1937): 20x40 -> 7200 | 48x20 ->
+# sum_splits<16 | 32 | 64> by wsize = 9 Cin Cout on each side of 8192 and 32768 (launch_sum_splits, conv_mfma_wgrad.hip): 20x40 -> 7200 | 48x20 ->
 # 8640 | 48x72 -> 31104 | 48x76 -> 32832; on 3x13x31 (<= 12 splits: the single-accumulator tail loop alone) and on 5x37x100 (175
 # tiles: 175 / 175 / 59 / 59 splits, past 3 * 256 / COLS: the four-accumulator loop and its tail)
 @pytest.mark.parametrize("plane", [(3, 13, 31), (5, 37, 100)], ids=["tail-loop", "4acc-loop"])
@@ -725,8 +725,8 @@ def test_lds_wgrad_cat_and_input_side_instnorm(H, n, h, w, ci, co, form, ca):
     assert kern == f"lds{cit}x{cot}"
 
 
-# plane_wgrad (conv_mfma.hip:3168-3171, 3203-3206): H W <= 64, W % 4 == 0, channels % 32 == 0, N H W <= 4096.  Planes 1x4, 2x4, 4x8,
-# 8x8 with odd N, plain and cat; N H W = 4096 exactly (64 x 8 x 8) and just past it (65 x 8 x 8 -> the 2x2 LDS kernel)
+# plane_wgrad (plane_wgrad_applies, conv_mfma_wgrad.hip): H W <= 64, W % 4 == 0, channels % 32 == 0, N H W <= 4096.  Planes 1x4, 2x4,
+# 4x8, 8x8 with odd N, plain and cat; N H W = 4096 exactly (64 x 8 x 8) and just past it (65 x 8 x 8 -> the 2x2 LDS kernel)
 @pytest.mark.parametrize("form", ["plain", "cat"])
 @pytest.mark.parametrize("n,h,w,ci,co,kernel", [(5, 1, 4, 32, 32, "plane"), (5, 2, 4, 64, 32, "plane"), (5, 4, 8, 32, 64, "plane"),
                                                (5, 8, 8, 32, 32, "plane"), (64, 8, 8, 32, 32, "plane"), (65, 8, 8, 32, 32, "lds2x2")])

@@ -358,10 +358,10 @@ def convT_ref(x, wt, gy):
 
 
 def convT_branch(N, Hh, W, ndim, ntap_out, transposed):
-    """dispatch_fwd<1> as the transposed conv reaches it (conv_mfma.hip:2281-2299; osc = 2 or isc = 2, so neither the 8x8-plane nor the
+    """dispatch_fwd<1> as the transposed conv reaches it (its launch_fwd rows, conv_mfma.hip; osc = 2 or isc = 2, so neither the 8x8-plane nor the
     `H <= 4 && isc == 1 && osc == 1` branch applies).  A restatement, checked against nothing in the library (the tile configuration
     has no query): whoever moves the wg16 >= 512 / wg8 >= 256 thresholds there must edit this function and the CONVT shapes with
-    them, or the case ids name a branch the cases no longer take.  The same holds for k4_nt (conv_mfma.hip:3590), flat_mt
+    them, or the case ids name a branch the cases no longer take.  The same holds for k4_nt (smsut_conv2d_k4_fwd, conv_mfma.hip), flat_mt
     (conv_small.hip:552-556) and is_stem (conv_small.hip:429-432) below."""
     nt, tx = cdiv(ndim, 16), cdiv(W, 16)
     wg16 = tx * cdiv(Hh, 16) * N * ((nt + 1) // 2) * ntap_out
@@ -376,7 +376,7 @@ def convT_branch(N, Hh, W, ndim, ntap_out, transposed):
 
 
 def plan_wgrad(N, Hh, W, ci, co, taps_k=9, tw=16, th=8):
-    """plan_wgrad (conv_mfma.hip:2653-2679): (cit, cot, splits, tiles_per_split)"""
+    """plan_wgrad (conv_mfma_wgrad.hip): (cit, cot, splits, tiles_per_split)"""
     cit, cot = (2 if ci > 16 else 1), (2 if co > 16 else 1)
     total = N * cdiv(W, tw) * cdiv(Hh, th)
     slabs = cdiv(ci, 16 * cit) * cdiv(co, 16 * cot)
@@ -387,7 +387,7 @@ def plan_wgrad(N, Hh, W, ci, co, taps_k=9, tw=16, th=8):
 
 
 def sum_splits_form(wsize, splits):
-    """launch_sum_splits (conv_mfma.hip:1928-1938): columns per block by wsize, and whether a lane enters the four-accumulator loop
+    """launch_sum_splits (conv_mfma_wgrad.hip): columns per block by wsize, and whether a lane enters the four-accumulator loop
     (`c + 3 LANES < splits`, LANES = 256 / COLS)"""
     cols = 64 if wsize >= 32768 else (32 if wsize >= 8192 else 16)
     return f"cols{cols}-{'4acc' if splits > 3 * (256 // cols) else 'tail'}"
@@ -555,12 +555,12 @@ def test_ops_conv_transpose2x2_is_the_direct_call(ops, H, ci, co, form):
 
 
 # ================================================================================================ 4. 4x4 stride 1 pad 1
-# smsut_conv2d_k4_fwd (conv_mfma.hip:3581-3601): NT = 2 (32-channel slabs) when Ndim % 32 == 0 || Ndim > 16, else NT = 1; forward Ndim =
+# smsut_conv2d_k4_fwd (conv_mfma.hip): NT = 2 (32-channel slabs) when Ndim % 32 == 0 || Ndim > 16, else NT = 1; forward Ndim =
 # Cout, Kdim = Cin, tiles over the (H-1) x (W-1) output; transposed Ndim = Cin, Kdim = Cout, pad 2, tiles over the H x W result.  Tiles
 # are 8 x 16.  The channel pairs give, forward | transposed:  Ndim 4, 16 -> NT 1;  20, 24 -> NT 2 with a ragged slab;  32 -> NT 2 exact;
 # 48 -> NT 2, ragged second slab;  64 -> two slabs.  Kdim 4: one partial chunk, 20: a partial second chunk, 64: four chunks.
-# Planes (H, W of the forward input): 2x2 -> a 1x1 output (every halo read is masked by in_off = -1, conv_mfma.hip:2461; the store by
-# gy_ < Ho, gx_ < Wo, :2524-2532) | 2x9 -> one output row | 9x10 -> output 8x9: one tile, exactly full rows | 17x33 -> output 16x32: 2 x 2
+# Planes (H, W of the forward input): 2x2 -> a 1x1 output (every halo read is masked by in_off = -1 in conv_k4_fwd, conv_mfma.hip; the store by
+# gy_ < Ho, gx_ < Wo in its epilogue) | 2x9 -> one output row | 9x10 -> output 8x9: one tile, exactly full rows | 17x33 -> output 16x32: 2 x 2
 # exactly full tiles forward, 3 x 3 tiles with one row and one column in the last ones transposed | 10x18 -> output 9x17: one row and one
 # column into the next tile forward.
 K4_CH = [(4, 4), (20, 16), (64, 20), (4, 24), (20, 32), (64, 48), (16, 4), (24, 20), (32, 64), (48, 4)]
@@ -572,7 +572,7 @@ def k4_nt(ndim):
 
 
 def plan_k4(N, Hh, W, ci, co):
-    """plan_wgrad_k4 (conv_mfma.hip:3602-3619): (cot, splits, tiles_per_split)"""
+    """plan_wgrad_k4 (conv_mfma_wgrad.hip): (cot, splits, tiles_per_split)"""
     cot = 2 if co > 16 else 1
     total = N * cdiv(W - 1, 16) * cdiv(Hh - 1, 8)
     slabs = cdiv(ci, 16) * cdiv(co, 16 * cot)
