@@ -780,6 +780,43 @@ int smsut_tta_expand(const uint8_t* img, float* out, const int* transforms, int 
 int smsut_tta_merge(const float* const* members, const int* transforms, uint8_t* pred, float* conf /*nullable*/,
                     float* prob /*nullable*/, int T, int N, int H, int W, int C, int K, void* stream);
 
+/* ---------------------------------------------------------------------------------------------- calibration
+ * How far the predicted probabilities of a batch can be trusted (csrc/calibration.hip; misc/utils.py: CalibrationMeter,
+ * fit_temperature): the reliability table, negative log-likelihood, Brier score and the derivatives of the NLL by the inverse
+ * temperature, in one pass.  The reference has no calibration code: this replaces the softmax / max / gather / bucketize /
+ * bincount / log / sum chain one would build from torch.
+ * logits fp32 [N][H][W][C] (NHWC), 4-byte aligned, read in place, each logit once; labels int64 [N][H][W]; classes = channels
+ * 0 .. K-1; B confidence bins; beta = 1 / temperature.  Per pixel with label y, all in fp32, in this order (z = the pixel's logits):
+ *   u_k = beta * z_k, rounded on its own (beta == 1.0f: u_k is z_k);   m = max_k u_k;   e_k = expf(u_k - m);
+ *   s = e_0 + e_1 + ... in channel order;   p_k = e_k / s;
+ *   pred = the first maximum of p_k by smsut_argmax_channels' comparison (the first maximum wins, a NaN wins);   conf = p_pred;
+ *   correct = (pred == y);   bin = min(B - 1, (int)(conf * (float)B));
+ *   nll = logf(s) - (u_y - m);
+ *   brier = sum_k (p_k - [k == y])^2,   ez = sum_k p_k z_k,   ezz = sum_k p_k (z_k z_k),   each in channel order from 0.0f (the
+ *     product of a term may be fused into its addition: one rounding less);   vz = max(ezz - ez ez, 0.0f).
+ * A pixel whose label lies outside 0 .. K-1 counts in `skipped` and nowhere else (smsut_eval_overlap's rule; its logits are not
+ * looked at); otherwise a pixel whose conf is NaN or Inf counts in `nonfinite` and nowhere else.
+ * out: double [3 B + 4 K + 4], ADDED to and never zeroed here (the caller zeroes it once per evaluation):
+ *   out[3 b + 0..2]          bin b:        {pixels, sum of conf, correct pixels}
+ *   out[3 B + 4 k + 0..3]    true class k: {pixels, correct pixels, sum of nll, sum of brier}
+ *   out[3 B + 4 K + 0..3]    {g = sum of (ez - z_y), h = sum of vz, skipped, nonfinite}
+ *   (ez - z_y is one fp32 subtraction; g and h are the first and second derivative of the summed NLL by beta).
+ * Counts are integers summed as integers; so is the sum of conf, as conf * 2^28 (an fp32 conf in [2^-5, 1] is a multiple of
+ * 2^-28), converted once: exact while it stays below 2^53 * 2^-28.  (A workgroup keeps pixels and correct pixels as the 32-bit
+ * halves of one word and the batch's sum of conf * 2^28 is one int64: both hold for any batch of fewer than 2^35 pixels, and a
+ * larger one -- more than 2^38 bytes of labels alone -- fits no device this library runs on; the limits below are per axis.)  nll, brier, ez - z_y and vz are converted to fp64 per pixel and
+ * summed in fp64 in an order that depends on (N H W, K) alone: per-workgroup partial vectors in `workspace`, added in workgroup
+ * order by a finishing launch.  No float atomics: two calls on the same input give the same bits.  Two launches, no memset.
+ * workspace: smsut_calibration_ws(N, H, W, C, K, B) bytes, written before it is read; -1 for arguments outside the limits.
+ * Limits (otherwise SMSUT_EINVAL and nothing is launched; N == 0 returns SMSUT_OK without a launch); beta finite and positive: */
+#define SMSUT_CALIB_MAX_CLASSES 32   /* 1 <= K <= min(C, 32) */
+#define SMSUT_CALIB_MAX_BINS 64      /* 1 <= B <= 64 */
+#define SMSUT_CALIB_MAX_SLICES 65535 /* N <= 65535 */
+#define SMSUT_CALIB_MAX_DIM 16384    /* 1 <= H, W <= 16384 */
+int64_t smsut_calibration_ws(int N, int H, int W, int C, int K, int B);
+int smsut_calibration_stats(const float* logits, const int64_t* labels, double* out, void* workspace, int N, int H, int W, int C,
+                            int K, int B, float beta, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

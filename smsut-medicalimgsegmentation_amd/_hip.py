@@ -255,12 +255,15 @@ SIGNATURES: Dict[str, str] = {
     # tta.hip (inference: test-time augmentation and ensembling)
     "smsut_tta_expand": "ppp iiii s",
     "smsut_tta_merge": "ppppp iiiiii s",
+    # calibration.hip (test phase: reliability, NLL, Brier, temperature fit)
+    "smsut_calibration_ws": "iiiiii",
+    "smsut_calibration_stats": "pppp iiiiii f s",
 }
 _RET_I64 = {"smsut_wino_image_floats", "smsut_conv2d_wgrad_pair_ws", "smsut_convT2x2_wgrad_ps_ws", "smsut_conv2d_wgrad_sc_ws", "smsut_conv2d_k4_wgrad_ws", "smsut_conv2d_wgrad_f16_ws", "smsut_conv2d_wgrad_sc_f16_ws", "smsut_absmax_scale_ws", "smsut_conv2d_wgrad_generic_ws", "smsut_colsum_ws", "smsut_dicece_ws", "smsut_sum_ws",
             "smsut_conv2d_wgrad_mfma_ws", "smsut_convT2x2_wgrad_mfma_ws", "smsut_conv2d_flat_wgrad_ws", "smsut_conv1x1_wgrad_ws",
             "smsut_conv1x1_thin_wgrad_ws", "smsut_cc_ws", "smsut_surface_ws", "smsut_surface_hd_ws", "smsut_surface_sp_ws", "smsut_surface_hd_sp_ws", "smsut_cora_ws",
             "smsut_sdf_ws", "smsut_dtc_ws", "smsut_image_similarity_ws",
-            "smsut_bspline_ws", "smsut_resample_ws", "smsut_order_statistics_ws"}
+            "smsut_bspline_ws", "smsut_resample_ws", "smsut_order_statistics_ws", "smsut_calibration_ws"}
 _NO_STATUS = _RET_I64 | {"smsut_conv2d_k4_supported", "smsut_conv2d_f16_supported", "smsut_conv2d_wgrad_f16_supported", "smsut_in_chunks", "smsut_in_slabs", "smsut_amax_blocks", "smsut_conv2d_mfma_supported", "smsut_conv2d_wgrad_mfma_supported",
                          "smsut_convT2x2_mfma_supported", "smsut_conv2d_small_supported",
                          "smsut_conv2d_flat_wgrad_supported", "smsut_conv2d_mfma_tiles", "smsut_conv2d_mfma_persistent", "smsut_conv1x1_supported",

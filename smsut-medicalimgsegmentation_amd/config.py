@@ -61,6 +61,10 @@ test_translation = False       # ugan trainers: -p test also writes {modality}_t
                                # before the loader is exhausted)
 test_translation_pairs = (('t1in', 't1out'),)   # modality-name pairs whose slices a_pid_z / b_pid_z show the same anatomy (CHAOS t1in /
                                # t1out are registered acquisitions); a pair whose modalities or slices are not in the test set adds nothing
+test_calibration = False       # -p test also writes {modality}_calibration.csv (reliability table, ECE / MCE / NLL / Brier / accuracy per
+                               # modality at T = 1 and at the temperature fitted on the test loader) and temperature.txt
+                               # (csrc/calibration.hip: one pass per batch, the batches' logits stay on the device for the fit)
+test_calibration_bins = 15     # confidence bins of equal width, 1 .. 64
 data_aug = dict(               # config.py:60-71
     rotate=True, rotate_degrees=15,
     resizeCrop=True, resizeCrop_size=input_size,

@@ -519,6 +519,280 @@ class TranslationMeter:
         return translation_tables(self.rows(), self._names, self._cells, self._shapes, self.data_range)
 
 
+# ------------------------------------------------------------------------------------------- calibration (test phase)
+# How far the network's probabilities can be trusted: expected / maximum calibration error (Guo et al. 2017: confidence bins of equal
+# width), negative log-likelihood, Brier score and the reliability table, from the totals of ``ops.calibration_stats``
+# (csrc/calibration.hip), and the one-parameter fix: a temperature fitted by Newton's method on the NLL.
+class CalibrationTotals:
+    """The calibration metrics of one totals vector of ``ops.calibration_stats`` (``ops.CalibrationLayout(classes, bins)``), in fp64
+    on the host.  With n = the counted pixels, and per bin b its pixels n_b, accuracy acc_b and mean confidence conf_b:
+    ECE = sum_b (n_b / n) |acc_b - conf_b|, MCE = the largest |acc_b - conf_b| of a non-empty bin; NLL, Brier and accuracy are
+    means over the counted pixels.  Everything is NaN when nothing was counted.  Pure host code."""
+
+    def __init__(self, totals, classes, bins):
+        from ..ops import CalibrationLayout
+        self.layout = CalibrationLayout(classes, bins)
+        self.totals = np.asarray(totals, dtype=np.float64)
+        if self.totals.shape != (self.layout.size,):
+            raise ValueError(f"CalibrationTotals: expected {self.layout.size} totals, got shape {self.totals.shape}")
+        self._bins, self._classes = self.layout.bins(self.totals), self.layout.classes(self.totals)
+
+    @property
+    def pixels(self):
+        return float(self._bins[:, 0].sum())
+
+    def _gaps(self):
+        """(pixels, |accuracy - mean confidence|) of the non-empty bins"""
+        has = self._bins[:, 0] > 0
+        n = self._bins[has, 0]
+        return n, np.abs(self._bins[has, 2] / n - self._bins[has, 1] / n)
+
+    def ece(self):
+        n, gap = self._gaps()
+        return float((n / n.sum() * gap).sum()) if n.size else float("nan")
+
+    def mce(self):
+        n, gap = self._gaps()
+        return float(gap.max()) if n.size else float("nan")
+
+    def _mean(self, total):
+        return float(total / self.pixels) if self.pixels else float("nan")
+
+    def nll(self):
+        return self._mean(self._classes[:, 2].sum())
+
+    def brier(self):
+        return self._mean(self._classes[:, 3].sum())
+
+    def accuracy(self):
+        return self._mean(self._bins[:, 2].sum())
+
+    def reliability(self):
+        """[bins, 5]: the bin's lower edge, upper edge, pixels, mean confidence, accuracy (NaN for an empty bin)."""
+        b = self.layout.n_bins
+        out = np.full((b, 5), np.nan)
+        out[:, 0], out[:, 1], out[:, 2] = np.arange(b) / b, (np.arange(b) + 1.0) / b, self._bins[:, 0]
+        has = self._bins[:, 0] > 0
+        out[has, 3], out[has, 4] = self._bins[has, 1] / self._bins[has, 0], self._bins[has, 2] / self._bins[has, 0]
+        return out
+
+    def per_class(self):
+        """[classes, 4] by TRUE class: pixels, accuracy (the class's recall), mean NLL, mean Brier (NaN for an absent class)."""
+        out = np.full((self.layout.n_classes, 4), np.nan)
+        out[:, 0] = self._classes[:, 0]
+        has = self._classes[:, 0] > 0
+        out[has, 1:] = self._classes[has, 1:] / self._classes[has, :1]
+        return out
+
+    def grad(self):
+        return float(self.layout.grad(self.totals))
+
+    def curv(self):
+        return float(self.layout.curv(self.totals))
+
+    def skipped(self):
+        return int(self.layout.skipped(self.totals))
+
+    def nonfinite(self):
+        return int(self.layout.nonfinite(self.totals))
+
+    def summary(self):
+        """(ECE, MCE, NLL, Brier, accuracy): one row of the test phase's table."""
+        return (self.ece(), self.mce(), self.nll(), self.brier(), self.accuracy())
+
+
+class CalibrationMeter:
+    """The calibration totals of one test pass, kept on the device: ``rows`` totals vectors (one per modality in the test phase;
+    one by default) in a single fp64 tensor.  ``update`` adds a batch into a row with one ``ops.calibration_stats`` call and reads
+    nothing back; the first metric asked for makes the ONE device-to-host copy (kept until the next ``update``).  Every metric takes
+    ``row``: one row, or None for the sum of all rows."""
+
+    def __init__(self, classes, bins=15, temperature=1.0, rows=1):
+        from .. import ops
+        self.layout = ops.CalibrationLayout(classes, bins)
+        ops.calibration_beta(temperature)
+        self.classes, self.bins, self.temperature, self.rows = int(classes), int(bins), float(temperature), int(rows)
+        if self.rows < 1:
+            raise ValueError(f"CalibrationMeter: needs at least one row, got {rows}")
+        self._dev, self._host = None, None
+
+    def update(self, out, msk, row=0):
+        """Add the batch ``out`` (logits, logical NCHW on the device) / ``msk`` (int64 [N, H, W]) into ``row``."""
+        import torch
+        from .. import ops
+        if not 0 <= int(row) < self.rows:
+            raise ValueError(f"CalibrationMeter: no row {row} of {self.rows}")
+        if not isinstance(out, torch.Tensor) or not out.is_cuda:
+            raise TypeError("CalibrationMeter: the logits must be a tensor on a HIP device (no CPU fallback)")
+        if self._dev is None:
+            self._dev = torch.zeros(self.rows, self.layout.size, dtype=torch.float64, device=out.device)
+        ops.calibration_stats(out, msk, self._dev[int(row)], classes=self.classes, bins=self.bins, temperature=self.temperature)
+        self._host = None
+
+    def totals(self):
+        """Everything counted so far as a float64 host array [rows, size]: one copy."""
+        if self._host is None:
+            self._host = np.zeros((self.rows, self.layout.size)) if self._dev is None else self._dev.cpu().numpy()
+        return self._host
+
+    def result(self, row=None):
+        t = self.totals()
+        return CalibrationTotals(t.sum(axis=0) if row is None else t[int(row)], self.classes, self.bins)
+
+    def ece(self, row=None):
+        return self.result(row).ece()
+
+    def mce(self, row=None):
+        return self.result(row).mce()
+
+    def nll(self, row=None):
+        return self.result(row).nll()
+
+    def brier(self, row=None):
+        return self.result(row).brier()
+
+    def accuracy(self, row=None):
+        return self.result(row).accuracy()
+
+    def reliability(self, row=None):
+        return self.result(row).reliability()
+
+    def per_class(self, row=None):
+        return self.result(row).per_class()
+
+
+def _device_logits(logits, labels, what):
+    """Logits [N, C, H, W] and labels [N, H, W] as ``ops.calibration_stats`` takes them.  Tensors are taken as they are when they
+    already are that (float32 / int64 on a HIP device), any other tensor raises ``TypeError``; NumPy arrays are uploaded (the logits
+    in NHWC memory)."""
+    import torch
+    from .._hip import SmsutHipError
+    if isinstance(logits, torch.Tensor) != isinstance(labels, torch.Tensor):
+        raise TypeError(f"{what}: logits and labels must both be tensors or both be arrays")
+    if isinstance(logits, torch.Tensor):
+        if logits.dtype != torch.float32 or labels.dtype != torch.int64 or not logits.is_cuda or not labels.is_cuda:
+            raise TypeError(f"{what}: tensors must be float32 logits and int64 labels on a HIP device, got {logits.dtype} on "
+                            f"{logits.device} and {labels.dtype} on {labels.device}")
+        return logits, labels
+    z, y = np.asarray(logits), np.asarray(labels)
+    if not np.issubdtype(z.dtype, np.floating) or not np.issubdtype(y.dtype, np.integer):
+        raise TypeError(f"{what}: expected floating logits and integer labels, got {z.dtype} and {y.dtype}")
+    if z.ndim != 4 or y.shape != (z.shape[0],) + z.shape[2:]:
+        raise ValueError(f"{what}: expected logits [N, C, H, W] and labels [N, H, W], got {z.shape} and {y.shape}")
+    if not torch.cuda.is_available():
+        raise SmsutHipError("the calibration metrics run on an MI355X (no HIP device visible; there is no CPU fallback)")
+    dev = torch.device("cuda", torch.cuda.current_device())
+    z = torch.from_numpy(np.ascontiguousarray(z.transpose(0, 2, 3, 1), dtype=np.float32)).to(dev).permute(0, 3, 1, 2)
+    return z, torch.from_numpy(np.ascontiguousarray(y, dtype=np.int64)).to(dev)
+
+
+def _calibration_of(logits, labels, classes, bins, temperature, what):
+    z, y = _device_logits(logits, labels, what)
+    meter = CalibrationMeter(z.shape[1] if classes is None else classes, bins, temperature)
+    meter.update(z, y)
+    return meter.result()
+
+
+def ece(logits, labels, bins=15, classes=None, temperature=1.0):
+    """Expected calibration error of one batch of logits [N, C, H, W] against labels [N, H, W] on the GPU (NumPy arrays or device
+    tensors -> Python float)."""
+    return _calibration_of(logits, labels, classes, bins, temperature, "ece").ece()
+
+
+def nll(logits, labels, classes=None, temperature=1.0):
+    """Mean negative log-likelihood of the labels under ``softmax(logits / temperature)``, on the GPU."""
+    return _calibration_of(logits, labels, classes, 1, temperature, "nll").nll()
+
+
+def brier(logits, labels, classes=None, temperature=1.0):
+    """Mean Brier score, sum_k (p_k - [k == y])^2 per pixel, on the GPU."""
+    return _calibration_of(logits, labels, classes, 1, temperature, "brier").brier()
+
+
+def newton_inverse_temperature(evaluate, tol=1e-6, max_iter=30):
+    """The safeguarded Newton iteration of the temperature fit, on beta = 1 / T from 1: ``evaluate(beta) -> (g, h)``, the first and
+    second derivative of the summed NLL by beta (the NLL is convex in beta: h >= 0).  beta <- beta - g / h; when that would not
+    leave beta > 0, or h is not positive, beta is halved instead.  Every iterate is rounded to float32, the format the kernel takes
+    it in.  Stops when |new - beta| <= tol * beta, or after ``max_iter`` evaluations.  Returns ``(beta, evaluations)``."""
+    beta = 1.0
+    for it in range(1, int(max_iter) + 1):
+        g, h = evaluate(beta)
+        new = beta - g / h if h > 0 else 0.0
+        if not new > 0:
+            new = 0.5 * beta
+        new = float(np.float32(new))
+        done = abs(new - beta) <= tol * beta
+        beta = new
+        if done:
+            break
+    return beta, it
+
+
+def fit_temperature(batches, classes, tol=1e-6, max_iter=30):
+    """Temperature scaling (Guo et al. 2017): the T that minimises the NLL of ``softmax(logits / T)`` over ``batches``, a sequence
+    of ``(logits, labels)`` pairs that stay on the device (``ops.calibration_stats``' arguments).  ``newton_inverse_temperature``
+    with one launch per batch and one read-back of the two derivatives per iteration.  Returns ``(T, iterations)``."""
+    import torch
+    from .. import ops
+    batches = list(batches)
+    if not batches:
+        raise ValueError("fit_temperature: no batches")
+    layout = ops.CalibrationLayout(classes, 1)
+    tail = slice(layout.size - 4, layout.size - 2)
+
+    def evaluate(beta):
+        out = torch.zeros(layout.size, dtype=torch.float64, device=batches[0][0].device)
+        for z, y in batches:
+            ops.calibration_stats(z, y, out, classes=layout.n_classes, bins=1, temperature=1.0 / beta)
+        g, h = out[tail].tolist()
+        return g, h
+
+    beta, its = newton_inverse_temperature(evaluate, tol, max_iter)
+    return 1.0 / beta, its
+
+
+CALIBRATION_COLUMNS = ("ECE", "MCE", "NLL", "Brier", "accuracy")
+
+
+def calibration_rows(meter):
+    """[rows + 1, 5]: ``CALIBRATION_COLUMNS`` of every row of a ``CalibrationMeter`` and, last, of all rows together."""
+    return np.array([meter.result(r).summary() for r in range(meter.rows)] + [meter.result().summary()])
+
+
+def calibration_text(reliability, rows_raw, rows_fitted):
+    """``{modality}_calibration.csv``: the reliability table (``CalibrationTotals.reliability``), an empty line, the
+    ``calibration_rows`` at T = 1, an empty line, the same rows at the fitted temperature; '%.6f' values separated by ','
+    (``nan`` as Python formats it)."""
+    block = lambda m: "".join(",".join("%.6f" % v for v in row) + "\n" for row in np.asarray(m, dtype=np.float64))
+    return block(reliability) + "\n" + block(rows_raw) + "\n" + block(rows_fitted)
+
+
+class CalibrationReport:
+    """What ``-p test`` gathers with ``cfg.test_calibration``: a ``CalibrationMeter`` at T = 1 with one row per modality, fed batch
+    by batch, and the batches themselves -- logits and labels stay on the device as the validation loop left them (no copy, no
+    second forward pass; 4 C bytes per pixel of the test set) -- for the temperature fit and the statistics at the fitted T."""
+
+    def __init__(self, rows, bins=15):
+        self.rows, self.bins = int(rows), int(bins)
+        self.meter, self.batches = None, []
+
+    def update(self, out, msk, row, classes=None):
+        if self.meter is None:
+            self.meter = CalibrationMeter(out.shape[1] if classes is None else classes, self.bins, rows=self.rows)
+        self.meter.update(out, msk, row)
+        self.batches.append((out, msk, int(row)))
+
+    def finish(self):
+        """``(text of the csv, fitted T, Newton iterations)``"""
+        if self.meter is None:
+            raise ValueError("CalibrationReport: no batch was fed")
+        t, its = fit_temperature([(o, m) for o, m, _ in self.batches], self.meter.classes)
+        fitted = CalibrationMeter(self.meter.classes, self.bins, temperature=t, rows=self.rows)
+        for o, m, r in self.batches:
+            fitted.update(o, m, r)
+        return calibration_text(self.meter.reliability(), calibration_rows(self.meter), calibration_rows(fitted)), t, its
+
+
 class Meter:
     """Running per-modality loss / dice with best tracking (utils.py:58-160), trimmed to what the trainers call."""
 

@@ -2933,3 +2933,102 @@ def tta_merge(members, transforms, classes=None, want_conf=False, want_prob=Fals
     H.call("smsut_tta_merge", ctypes.addressof(ptrs), addr, pred, conf, prob, len(zs), n, h, w, c, k, _s())
     del keep, ptrs
     return pred, conf, prob
+
+
+# ------------------------------------------------------------------------------------------- calibration (test phase)
+CALIB_MAX_CLASSES, CALIB_MAX_BINS, CALIB_MAX_SLICES, CALIB_MAX_DIM = 32, 64, 65535, 16384   # include/smsut_hip.h: SMSUT_CALIB_*
+
+
+class CalibrationLayout:
+    """Where ``calibration_stats`` keeps what in its fp64 vector of ``size = 3 bins + 4 classes + 4`` (include/smsut_hip.h).
+    Each accessor takes such a vector -- a NumPy array or a tensor, anything that slices -- and returns a view:
+    ``bins`` ``[bins, 3]`` = {pixels, sum of conf, correct pixels}; ``classes`` ``[classes, 4]`` = {pixels, correct pixels, sum of
+    nll, sum of brier} per true class; ``grad``, ``curv`` (the first and second derivative of the summed NLL by 1 / temperature),
+    ``skipped`` and ``nonfinite``: the element itself.  Pure host code."""
+
+    def __init__(self, classes, bins):
+        self.n_classes, self.n_bins = int(classes), int(bins)
+        if not 1 <= self.n_classes <= CALIB_MAX_CLASSES:
+            raise ValueError(f"CalibrationLayout: classes must lie in 1..{CALIB_MAX_CLASSES}, got {classes}")
+        if not 1 <= self.n_bins <= CALIB_MAX_BINS:
+            raise ValueError(f"CalibrationLayout: bins must lie in 1..{CALIB_MAX_BINS}, got {bins}")
+        self.size = 3 * self.n_bins + 4 * self.n_classes + 4
+        self._tail = 3 * self.n_bins + 4 * self.n_classes
+
+    def bins(self, v):
+        return v[:3 * self.n_bins].reshape(self.n_bins, 3)
+
+    def classes(self, v):
+        return v[3 * self.n_bins:self._tail].reshape(self.n_classes, 4)
+
+    def grad(self, v):
+        return v[self._tail]
+
+    def curv(self, v):
+        return v[self._tail + 1]
+
+    def skipped(self, v):
+        return v[self._tail + 2]
+
+    def nonfinite(self, v):
+        return v[self._tail + 3]
+
+
+def calibration_stats(logits, labels, out, classes=None, bins=15, temperature=1.0):
+    """Calibration statistics of one batch in one pass (csrc/calibration.hip), ADDED into ``out``: fp64, contiguous,
+    ``CalibrationLayout(classes, bins).size`` elements on the logits' device; the caller zeroes it once.  ``logits``: logical NCHW
+    fp32 in the NHWC memory a network leaves it in (read in place, no copy); ``labels``: int64 ``[N, H, W]``; ``classes``: the
+    leading channels that are classes (default: all; CoraNet passes L + 1); the softmax is taken of ``logits / temperature``
+    (the kernel multiplies by the fp32 value of ``1 / temperature``).  A label outside ``0 .. classes-1`` counts in ``skipped``
+    only.  Two launches, nothing is read back; bitwise reproducible.  Returns ``out``.  Wrong types raise ``TypeError``, wrong
+    shapes or values ``ValueError``, before the device is touched.  No CPU fallback."""
+    for what, t, dt in (("logits", logits, torch.float32), ("labels", labels, torch.int64), ("out", out, torch.float64)):
+        if not isinstance(t, torch.Tensor):
+            raise TypeError(f"calibration_stats: {what} must be a tensor, got {type(t).__name__}")
+        if t.dtype != dt:
+            raise TypeError(f"calibration_stats: {what} must be {dt}, got {t.dtype}")
+        if not t.is_cuda or t.device != logits.device:
+            raise TypeError(f"calibration_stats: {what} must be on the logits' HIP device, got {t.device} (no CPU fallback)")
+    for what, v in (("bins", bins), ("classes", classes)):
+        if v is not None and (isinstance(v, bool) or not isinstance(v, int)):
+            raise TypeError(f"calibration_stats: {what} must be an int, got {type(v).__name__}")
+    if isinstance(temperature, bool) or not isinstance(temperature, (int, float)):
+        raise TypeError(f"calibration_stats: temperature must be a number, got {type(temperature).__name__}")
+    if logits.dim() != 4:
+        raise ValueError(f"calibration_stats: expected NCHW logits, got shape {tuple(logits.shape)}")
+    n, c, h, w = logits.shape
+    k = c if classes is None else classes
+    if not 1 <= k <= min(c, CALIB_MAX_CLASSES):
+        raise ValueError(f"calibration_stats: classes must lie in 1..min(C, {CALIB_MAX_CLASSES}), got {k} with C = {c}")
+    if not 1 <= bins <= CALIB_MAX_BINS:
+        raise ValueError(f"calibration_stats: bins must lie in 1..{CALIB_MAX_BINS}, got {bins}")
+    beta = calibration_beta(temperature)
+    if tuple(labels.shape) != (n, h, w):
+        raise ValueError(f"calibration_stats: labels must be [N, H, W] = {(n, h, w)}, got {tuple(labels.shape)}")
+    size = CalibrationLayout(k, bins).size
+    if out.dim() != 1 or out.shape[0] != size or not out.is_contiguous():
+        raise ValueError(f"calibration_stats: out must be a contiguous vector of {size} elements, got {tuple(out.shape)}")
+    if n > CALIB_MAX_SLICES or not (1 <= h <= CALIB_MAX_DIM and 1 <= w <= CALIB_MAX_DIM):
+        raise ValueError(f"calibration_stats: needs at most {CALIB_MAX_SLICES} slices with H, W in 1..{CALIB_MAX_DIM}, got {(n, h, w)}")
+    if n == 0:
+        return out
+    z = nhwc(logits.detach())                                  # (a network's output already is NHWC: no copy)
+    nbytes = H.call("smsut_calibration_ws", n, h, w, c, k, bins)
+    ws = _byte_ws(nbytes, z)
+    H.call("smsut_calibration_stats", z, labels.contiguous(), out, ws, n, h, w, c, k, bins, beta, _s())
+    return out
+
+
+def calibration_beta(temperature):
+    """The fp32 inverse temperature the kernel multiplies by: ``float32(1 / temperature)``; ``ValueError`` unless the temperature
+    and that value are finite and positive."""
+    import math
+    import numpy as _np
+    t = float(temperature)
+    if not (math.isfinite(t) and t > 0.0):
+        raise ValueError(f"calibration: temperature must be finite and positive, got {temperature}")
+    with _np.errstate(over="ignore"):
+        beta = float(_np.float32(1.0 / t))
+    if not (math.isfinite(beta) and beta > 0.0):
+        raise ValueError(f"calibration: 1 / temperature = {1.0 / t} is not a positive finite float32")
+    return beta

@@ -11,6 +11,7 @@ phase's 3-D connected-component cleanup in between.  Everything stays on the dev
 needs a PNG tree, a split yaml and ground truth (trainer/baseTrainer.py:254-318).
 """
 import argparse
+import numbers
 import os
 import types
 from typing import NamedTuple, Optional
@@ -52,9 +53,16 @@ class Predictor:
     Slices are processed in groups of ``batch_size``: one ``tta_expand`` launch, one forward of ``batch_size`` images per (network,
     transform), one ``tta_merge`` launch.  The last group is padded with zero images to ``batch_size`` (as ``validate_epoch`` pads
     it: captured graphs are per shape) and the padding is dropped.  Working memory is one group's members, not the volume's; nothing
-    is read back.  With one member and no confidence the prediction is ``ops.argmax_channels``' and the merge kernel does not run."""
+    is read back.  With one member and no confidence the prediction is ``ops.argmax_channels``' and the merge kernel does not run.
 
-    def __init__(self, forward, batch_size=None, tta="none", classes=None):
+    ``temperature``: temperature scaling (``misc.utils.fit_temperature``; the ``temperature.txt`` of ``-p test`` with
+    ``cfg.test_calibration``): one T for every forward, or one per forward of an ensemble.  A forward's logits are multiplied by the
+    fp32 value of 1 / T (one elementwise launch per member) before ``ops.tta_merge``, which makes the averaged probabilities and
+    the confidence those of the calibrated networks.  A forward whose T is None or 1 is left untouched: with no other T the path,
+    and its output, are bit for bit those of a ``Predictor`` without the argument.  The one-member argmax is taken from the
+    unscaled logits: a positive scale does not move it."""
+
+    def __init__(self, forward, batch_size=None, tta="none", classes=None, temperature=None):
         self.forwards = list(forward) if isinstance(forward, (list, tuple)) else [forward]
         if not self.forwards or not all(callable(f) for f in self.forwards):
             raise TypeError("Predictor: forward must be a callable or a non-empty list of callables")
@@ -64,6 +72,22 @@ class Predictor:
         self.transforms = ops.tta_transforms(tta)
         self.classes = None if classes is None else int(classes)
         self.members = len(self.forwards) * len(self.transforms)
+        if isinstance(temperature, bool):
+            raise TypeError("Predictor: temperature must be a number, a sequence of numbers or None, got a bool")
+        if temperature is None or isinstance(temperature, numbers.Real):
+            temperature = [temperature] * len(self.forwards)
+        try:
+            temperature = list(temperature)
+        except TypeError:
+            raise TypeError(f"Predictor: temperature must be a number, a sequence of numbers or None, got "
+                            f"{type(temperature).__name__}") from None
+        for t in temperature:
+            if t is not None and (isinstance(t, bool) or not isinstance(t, numbers.Real)):
+                raise TypeError(f"Predictor: a temperature must be a number or None, got {type(t).__name__}")
+        if len(temperature) != len(self.forwards):
+            raise ValueError(f"Predictor: {len(temperature)} temperatures for {len(self.forwards)} forwards")
+        # per forward: None (untouched) or the fp32 inverse temperature its logits are multiplied by
+        self.scales = [None if t is None or float(t) == 1.0 else ops.calibration_beta(t) for t in temperature]
         if self.members > ops.TTA_MAX_MEMBERS:
             raise ValueError(f"Predictor: {len(self.forwards)} networks x {len(self.transforms)} transforms = {self.members} members, "
                              f"at most {ops.TTA_MAX_MEMBERS}")
@@ -101,6 +125,9 @@ class Predictor:
                 if len(outs) == 1 and not confidence and k == outs[0].shape[1]:
                     pred[start:start + count] = ops.argmax_channels(outs[0])
                 else:
+                    if any(s is not None for s in self.scales):
+                        scale = [s for s in self.scales for _ in range(len(tr))]
+                        outs = [o if s is None else o * s for o, s in zip(outs, scale)]
                     p, c, _ = ops.tta_merge(outs, tr * len(self.forwards), classes=k, want_conf=confidence)
                     pred[start:start + count] = p
                     if confidence:
@@ -145,9 +172,26 @@ def make_parser():
     p.add_argument("--modality", required=True, help="'ct' windows to [-1000, 400]; any other name to the 0.05 / 99.5 percentiles")
     p.add_argument("--tta", default="none", choices=sorted(ops.TTA_SETS))
     p.add_argument("--confidence", action="store_true", help="also write confidence.npy (processed grid)")
+    p.add_argument("--temperature", default=None, help="temperature scaling of the probabilities: a number, or the path of the "
+                   "temperature.txt that -p test writes with config.test_calibration")
     p.add_argument("--batch_size", type=int, default=None)
     p.add_argument("--out", required=True, help="directory for labels.npy, labels_processed.npy (and confidence.npy)")
     return p
+
+
+def read_temperature(arg):
+    """``--temperature``: None, a number, or the path of a file whose first word is one (``temperature.txt``)."""
+    if arg is None:
+        return None
+    try:
+        return float(arg)
+    except ValueError:
+        pass
+    with open(arg) as f:
+        words = f.read().split()
+    if not words:
+        raise ValueError(f"--temperature: {arg} is empty")
+    return float(words[0])
 
 
 def trainer_forwards(trainer):
@@ -165,7 +209,8 @@ def main(argv=None):
     t = trainer_cls("test", types.SimpleNamespace(fold=0, expr_name=args.expr_name, model_id=args.model_id, write_env=False))
     t.load_model(args.model_id, args.which_ckpt)
     t.net.to(t.device)
-    predictor = Predictor(trainer_forwards(t), batch_size=args.batch_size, tta=args.tta, classes=cfg.n_label + 1)
+    predictor = Predictor(trainer_forwards(t), batch_size=args.batch_size, tta=args.tta, classes=cfg.n_label + 1,
+                          temperature=read_temperature(args.temperature))
     image = np.load(args.image)
     res = predict_volume(predictor, image, tuple(args.spacing), args.modality, confidence=args.confidence)
     os.makedirs(args.out, exist_ok=True)

@@ -384,6 +384,20 @@ class BaseTrainer(abc.ABC):
     def _forward_eval(self, img):
         return self.net(img)
 
+    # ------------------------------------------------------------------ calibration of the test phase (cfg.test_calibration)
+    _calibration = None            # a misc.utils.CalibrationReport while ``test`` runs its validation loop with the flag on
+
+    def _eval_classes(self, out):
+        """The leading channels of ``out`` that are classes, or None for all of them (coraNetTrainer: head 0)."""
+        return None
+
+    def _calibration_feed(self, out, msk, mdl):
+        """The validation loops' hook: one ``ops.calibration_stats`` call on the batch they hold (``msk`` on the device), counted
+        for the batch's modality ``mdl[0]`` as the meter counts its loss; nothing is read back.  Nothing happens outside a
+        ``test`` with ``cfg.test_calibration``."""
+        if self._calibration is not None:
+            self._calibration.update(out, msk, int(mdl[0].item()), self._eval_classes(out))
+
     def validate_epoch(self, loader, npys, meter=None, save_path=None):
         """baseTrainer.py:207-244 / uganShp0Trainer.py:250-287: no-grad inference, last batch padded to
         cfg.batch_size, on-GPU argmax, volume assembly by name 'm_pid_z'."""
@@ -398,10 +412,12 @@ class BaseTrainer(abc.ABC):
                 out = self._forward_eval(img)
                 if b != cfg.batch_size:
                     out = out[:b]
-                loss = self.loss(out, msk.to(self.device))
+                msk = msk.to(self.device)
+                loss = self.loss(out, msk)
                 if meter is not None:
                     v, n = meter.collect_loss_by(loss.item(), mdl[0].item(), img.size(0))
                     meter.accumulate(v, n)
+                self._calibration_feed(out, msk, mdl)
                 pred = ops.argmax_channels(out).cpu().numpy()
                 for i in range(b):
                     m, pid, z = inm[i].split("_")
@@ -458,6 +474,7 @@ class BaseTrainer(abc.ABC):
                     losses.append(loss.detach().reshape(-1)[0])
                     meter_args.append((mdl[0].item(), img.size(0)))
                 pred = counter.update(out, msk, inm[:b], classes=classes, want_pred=keep_volumes)
+                self._calibration_feed(out, msk, mdl)
                 if keep_volumes:
                     for i in range(b):
                         m, pid, z = inm[i].split("_")
@@ -497,8 +514,38 @@ class BaseTrainer(abc.ABC):
         With ``cfg.test_hausdorff`` also ``{modality}_hd_matrix.csv`` (the file the reference left commented out, :293-303):
         the Hausdorff rows, an empty line, then the HD95 rows of ``get_hd_matrix``, in the same layout and logged too.
         With ``cfg.test_spacing`` (one (sz, sy, sx), or a mapping by volume key or modality name) the ASSD, Hausdorff and HD95
-        rows are in that spacing's unit and the log says which spacing was used; None: voxels, the same bytes as ever."""
+        rows are in that spacing's unit and the log says which spacing was used; None: voxels, the same bytes as ever.
+        With ``cfg.test_calibration`` also ``{modality}_calibration.csv`` and ``temperature.txt`` (``calibration_report``)."""
         _, _, loader = self.get_loaders(loader_type)
+        if cfg.test_calibration:
+            from ..misc.utils import CalibrationReport
+            self._calibration = CalibrationReport(cfg.n_modal, cfg.test_calibration_bins)
+        try:
+            mo = self._test_tables(loader, expr_root)
+            if self._calibration is not None:
+                self.calibration_report(self._calibration, expr_root)
+        finally:
+            self._calibration = None
+        return mo
+
+    def calibration_report(self, report, expr_root):
+        """The calibration of the test set from what the validation loop fed into ``report`` (misc/utils.py: CalibrationReport; the
+        batches' logits were kept on the device, there is no second forward pass): ``{modality}_calibration.csv`` -- the reliability
+        table at T = 1 (rows: bin lower edge, upper edge, pixels, mean confidence, accuracy), an empty line, one row of ECE, MCE,
+        NLL, Brier, accuracy per modality and one for all of them at T = 1, an empty line, the same rows at the temperature
+        fitted on these batches (``fit_temperature``) -- also logged, and ``temperature.txt`` with that temperature, which
+        ``python -m smsut_amd.predict --temperature`` takes.  Returns ``(text, T)``."""
+        text, t, its = report.finish()
+        with open(pjoin(expr_root, f"{self.modality}_calibration.csv"), "w") as f:
+            f.write(text)
+        with open(pjoin(expr_root, "temperature.txt"), "w") as f:
+            f.write(f"{t!r}\n")
+        self.info(f"calibration ({report.bins} bins; ECE, MCE, NLL, Brier, accuracy per modality and overall, at T = 1 and at the "
+                  f"fitted T = {t:.6f}, {its} Newton iterations)")
+        self.info(text)
+        return text, t
+
+    def _test_tables(self, loader, expr_root):
         if cfg.validate_on_device:
             # counts and volumes stay on the device: ``dice_matrix.csv`` from the counts, the cleanup and surface kernels on the
             # volumes as assembled there; predictions leave the GPU only as the matrices below

@@ -280,10 +280,12 @@ class coraNetTrainer(BaseTrainer):
                 out = self._forward_eval(img)
                 if b != cfg.batch_size:
                     out = out[:b]
-                loss = self.sup_loss(out, msk.to(self.device))[0]
+                msk = msk.to(self.device)
+                loss = self.sup_loss(out, msk)[0]
                 if meter is not None:
                     v, n = meter.collect_loss_by(loss.item(), mdl[0].item(), img.size(0))
                     meter.accumulate(v, n)
+                self._calibration_feed(out, msk, mdl)
                 pred = ops.cora_pseudo(out)[0].cpu().numpy()
                 for i in range(b):
                     m, pid, z = inm[i].split("_")
@@ -294,6 +296,9 @@ class coraNetTrainer(BaseTrainer):
     def _eval_loss(self, out, msk):
         """``validate_epoch_device``'s hook: the three-head supervised loss, and head 0 (channels 0 .. L of the 3L+1) predicts."""
         return self.sup_loss(out, msk)[0], (out.shape[1] - 1) // 3 + 1
+
+    def _eval_classes(self, out):
+        return (out.shape[1] - 1) // 3 + 1
 
     def save_pseudo(self, loader_type, expr_root):
         """``-p pseudo``: pseudo labels and certainty masks of the unlabelled slices as ``pseudo/{plab,mask}.npy`` (uint8)."""
