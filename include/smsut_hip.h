@@ -779,6 +779,23 @@ int smsut_window_u8(const float* v, const float* bounds, uint8_t* out, int64_t n
 int smsut_tta_expand(const uint8_t* img, float* out, const int* transforms, int T, int N, int H, int W, void* stream);
 int smsut_tta_merge(const float* const* members, const int* transforms, uint8_t* pred, float* conf /*nullable*/,
                     float* prob /*nullable*/, int T, int N, int H, int W, int C, int K, void* stream);
+/* smsut_tta_uncertain (csrc/uncertainty.hip): the merge's pass with the uncertainty of the prediction.  Inputs, limits, tiles and
+ *   staging are smsut_tta_merge's (C <= 8 and K in 2..5: 32 x 32 tiles staged through LDS; other C <= 32: 16 x 16 staged; C > 32:
+ *   16 x 16, rows read in place); pred and conf are bitwise what smsut_tta_merge writes.  Per output pixel, all fp32, member by
+ *   member in list order: z = member[F_g(q)][0..K-1]; a_t = the first maximum of z (smsut_argmax_channels' comparison);
+ *   m = max_k z_k; e_k = expf(z_k - m); s = e_0 + e_1 + ... in channel order; q_k = e_k / s; acc_k += q_k;
+ *   h_t = -(q_0 logf(q_0 + 1e-6f) + q_1 logf(q_1 + 1e-6f) + ...), terms added in channel order; hs += h_t.  Then
+ *   mean_k = acc_k / (float)T; pred = the first maximum of mean; conf = mean_pred;
+ *   entropy = H = -(mean_0 logf(mean_0 + 1e-6f) + ...) in channel order; EH = hs / (float)T; mutual = fmaxf(H - EH, 0.f);
+ *   votes = #{t : a_t == pred}.  pred uint8, conf / entropy / mutual fp32, votes uint8, all [N][H][W]; all nullable but pred.
+ *   counts (nullable) int64 [K][2 T + 4], contiguous, ADDED into (the caller zeroes it once per volume); row k =
+ *   {V, ALL, ANY, HSUM, V_0 .. V_{T-1}, I_0 .. I_{T-1}}: V pixels with pred == k; ALL pixels where every a_t == k; ANY pixels where
+ *   some a_t == k; V_t pixels with a_t == k; I_t pixels with a_t == k and pred == k; HSUM the sum over pixels with pred == k of
+ *   (int64)rintf(H * 1048576.f), a pixel whose H is not finite adding nothing (it still counts in the other slots).  Integer
+ *   atomics only: bitwise reproducible. */
+int smsut_tta_uncertain(const float* const* members, const int* transforms, uint8_t* pred, float* conf /*nullable*/,
+                        float* entropy /*nullable*/, float* mutual /*nullable*/, uint8_t* votes /*nullable*/,
+                        int64_t* counts /*nullable*/, int T, int N, int H, int W, int C, int K, void* stream);
 
 /* ---------------------------------------------------------------------------------------------- calibration
  * How far the predicted probabilities of a batch can be trusted (csrc/calibration.hip; misc/utils.py: CalibrationMeter,

@@ -255,6 +255,8 @@ SIGNATURES: Dict[str, str] = {
     # tta.hip (inference: test-time augmentation and ensembling)
     "smsut_tta_expand": "ppp iiii s",
     "smsut_tta_merge": "ppppp iiiiii s",
+    # uncertainty.hip (inference: entropy, mutual information, votes and agreement counts in the merge's pass)
+    "smsut_tta_uncertain": "pppppppp iiiiii s",
     # calibration.hip (test phase: reliability, NLL, Brier, temperature fit)
     "smsut_calibration_ws": "iiiiii",
     "smsut_calibration_stats": "pppp iiiiii f s",

@@ -33,34 +33,12 @@
 // Tile: 32 x 32 with four pixels per lane when C <= 8 and K is one of the compile-time class counts (640-byte spans at C = 5, 20 KB
 // of LDS), else 16 x 16 with one pixel per lane (the accumulators of 32 runtime classes times four pixels would not fit the
 // register budget, and 32 rows of 32 x 33 floats would not fit LDS).  C > 32: the K <= 32 leading floats of each long row are read
-// in place, as evaluate.hip does.
-#include "common.h"
-#include "smsut_hip.h"
+// in place, as evaluate.hip does.  The member table, tta_pos and the staging copy live in tta_stage.h, which k_tta_uncertain
+// (uncertainty.hip) shares.
+#include "tta_stage.h"
 
 namespace {
-constexpr int TPB = 256;
-constexpr int MAXT = SMSUT_TTA_MAX_MEMBERS;
-constexpr int MAXK = SMSUT_TTA_MAX_CLASSES;
-constexpr int STAGE_MAXC = 32;         // rows of up to this many channels go through LDS; longer rows are read in place
-// Largest C that takes the 32 x 32 tile (a compile-time switch for the tile A/B of profiles/tta_notes.md: 0 = 16 x 16 everywhere).
-#ifndef SMSUT_TTA_TILE32_MAXC
-#define SMSUT_TTA_TILE32_MAXC 8
-#endif
-constexpr int TILE32_MAXC = SMSUT_TTA_TILE32_MAXC;
-
-struct TtaMembers { const float* z[MAXT]; unsigned char g[MAXT]; };
 struct TtaList { unsigned char g[MAXT]; };
-
-// (a, b) = the position in F_g(x) of pixel (i, j) of x [H][W]
-__device__ __forceinline__ void tta_pos(int g, int H, int W, int i, int j, int& a, int& b) {
-  const int jf = (g & 4) ? W - 1 - j : j;
-  switch (g & 3) {
-    case 0: a = i; b = jf; break;
-    case 1: a = W - 1 - jf; b = i; break;
-    case 2: a = H - 1 - i; b = W - 1 - jf; break;
-    default: a = jf; b = H - 1 - i; break;
-  }
-}
 
 __global__ void __launch_bounds__(TPB)
 k_tta_expand(const uint8_t* __restrict__ img, float* __restrict__ out, TtaList list, int64_t total, int N, int H, int W) {
@@ -98,8 +76,6 @@ k_tta_merge(TtaMembers mem, uint8_t* __restrict__ pred, float* __restrict__ conf
             int K) {
   constexpr int TS = PPL == 4 ? 32 : 16;
   constexpr int KK = KT ? KT : MAXK;
-  constexpr int LPR = 16, RPP = TPB / LPR;                   // staging: 16 lanes per member row, 16 rows per pass
-  constexpr int PASSES = TS / RPP, UNR = 4;
   extern __shared__ __attribute__((aligned(16))) float smem[];
   if (KT) K = KT;
   const int n = blockIdx.z;
@@ -107,7 +83,6 @@ k_tta_merge(TtaMembers mem, uint8_t* __restrict__ pred, float* __restrict__ conf
   const int th = min(TS, H - oy0), tw = min(TS, W - ox0);
   const int CP = C | 1, RS = TS * CP + 1;
   const int lx = threadIdx.x % TS, ly = threadIdx.x / TS;    // this lane's pixels: (oy0 + ly + p * (TPB / TS), ox0 + lx)
-  const int tx = threadIdx.x % LPR, ty = threadIdx.x / LPR;
   float acc[PPL][KK];
 #pragma unroll
   for (int p = 0; p < PPL; ++p)
@@ -122,60 +97,7 @@ k_tta_merge(TtaMembers mem, uint8_t* __restrict__ pred, float* __restrict__ conf
     tta_pos(g, H, W, oy0 + th - 1, ox0 + tw - 1, a1, b1);
     const int ma0 = min(a0, a1), mb0 = min(b0, b1);
     const int mh = (g & 1) ? tw : th, mw = (g & 1) ? th : tw;
-    if (STAGED) {
-      const int mis = (int)(((uintptr_t)z >> 2) & 3);        // floats of z past a 16-byte boundary
-      const int len = mw * C;
-      __syncthreads();                                       // the previous member's tile has been read
-      for (int u0 = tx; u0 * 4 < len + 3; u0 += LPR * UNR) { // (one round for TS * C <= 253 floats: every C <= 7 at TS = 32)
-        float4 v[PASSES][UNR];
-        int head[PASSES];
-#pragma unroll
-        for (int ps = 0; ps < PASSES; ++ps) {
-          const int r = ty + ps * RPP;
-          const int64_t s = (((int64_t)n * H + ma0 + (r < mh ? r : 0)) * W + mb0) * C;   // first float of the row's span
-          head[ps] = (int)((s + mis) & 3);                   // floats between the 16-byte boundary below the span and its start
-          const float* src = z + (s - head[ps]);
-#pragma unroll
-          for (int q = 0; q < UNR; ++q) {
-            const int i = (u0 + q * LPR) * 4;
-            v[ps][q] = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (r < mh && i < head[ps] + len) {
-              if (i >= head[ps] && i + 4 <= head[ps] + len) {
-                v[ps][q] = *(const float4*)(src + i);
-              } else {
-                float e[4] = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-                for (int c = 0; c < 4; ++c)
-                  if (i + c >= head[ps] && i + c < head[ps] + len) e[c] = src[i + c];
-                v[ps][q] = make_float4(e[0], e[1], e[2], e[3]);
-              }
-            }
-          }
-        }
-#pragma unroll
-        for (int ps = 0; ps < PASSES; ++ps) {
-          const int r = ty + ps * RPP;
-          float* dst = smem + r * RS;
-#pragma unroll
-          for (int q = 0; q < UNR; ++q) {
-            const int j0 = (u0 + q * LPR) * 4 - head[ps];    // the span's float index of v.x
-            const float e[4] = {v[ps][q].x, v[ps][q].y, v[ps][q].z, v[ps][q].w};
-            if (r < mh) {
-#pragma unroll
-              for (int c = 0; c < 4; ++c) {
-                const int j = j0 + c;
-                if (j >= 0 && j < len) {
-                  int o = j;
-                  if (CP != C) { const int px = (int)((unsigned)j / (unsigned)C); o = j + px; }   // px * CP + (j - px * C)
-                  dst[o] = e[c];
-                }
-              }
-            }
-          }
-        }
-      }
-      __syncthreads();
-    }
+    if (STAGED) tta_stage_tile<TS>(smem, z, n, H, W, C, ma0, mb0, mh, mw);
 #pragma unroll
     for (int p = 0; p < PPL; ++p) {
       const int oy = ly + p * (TPB / TS), ox = lx;
@@ -224,14 +146,6 @@ k_tta_merge(TtaMembers mem, uint8_t* __restrict__ pred, float* __restrict__ conf
   }
 }
 
-bool tta_list_ok(const int* transforms, int T, int H, int W) {
-  for (int t = 0; t < T; ++t) {
-    const int g = transforms[t];
-    if (g < 0 || g > 7 || ((g & 1) && H != W)) return false;
-  }
-  return true;
-}
-
 }  // namespace
 
 extern "C" {
@@ -262,11 +176,10 @@ int smsut_tta_merge(const float* const* members, const int* transforms, uint8_t*
     mem.z[t] = members[t];
     mem.g[t] = (unsigned char)transforms[t];
   }
-  const bool staged = C <= STAGE_MAXC;
-  const bool big = staged && C <= TILE32_MAXC && K >= 2 && K <= 5;
-  const int ts = big ? 32 : 16;
-  const dim3 grid((unsigned)((W + ts - 1) / ts), (unsigned)((H + ts - 1) / ts), (unsigned)N);
-  const size_t lds = staged ? (size_t)ts * (size_t)(ts * (C | 1) + 1) * sizeof(float) : 0;
+  const TtaTiling tl = tta_tiling(C, K);
+  const bool staged = tl.staged, big = tl.big;
+  const dim3 grid((unsigned)((W + tl.ts - 1) / tl.ts), (unsigned)((H + tl.ts - 1) / tl.ts), (unsigned)N);
+  const size_t lds = tl.tile_bytes;
 #define TTA_L(KT, PPL, ST) k_tta_merge<KT, PPL, ST><<<grid, TPB, lds, (hipStream_t)stream>>>(mem, pred, conf, prob, T, H, W, C, K)
 #define TTA_K(KT) do { if (big) TTA_L(KT, 4, true); else if (staged) TTA_L(KT, 1, true); else TTA_L(KT, 1, false); } while (0)
   switch (K) { case 2: TTA_K(2); break; case 3: TTA_K(3); break; case 4: TTA_K(4); break; case 5: TTA_K(5); break;

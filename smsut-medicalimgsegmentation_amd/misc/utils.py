@@ -9,6 +9,7 @@ upstream, the translator's metrics: ``ssim`` / ``psnr`` / ``mae``, ``Translation
 import os
 from collections import OrderedDict
 from copy import deepcopy
+from typing import NamedTuple
 
 import numpy as np
 
@@ -791,6 +792,57 @@ class CalibrationReport:
         for o, m, r in self.batches:
             fitted.update(o, m, r)
         return calibration_text(self.meter.reliability(), calibration_rows(self.meter), calibration_rows(fitted)), t, its
+
+
+class StructureAgreement(NamedTuple):
+    dice_agreement: np.ndarray                 # [K] mean over members of the Dice of the member's structure with the prediction's
+    iou_all: np.ndarray                        # [K] voxels every member gave the class / voxels some member gave it
+    volume_cv: np.ndarray                      # [K] population standard deviation of the members' volumes / their mean
+    mean_entropy: np.ndarray                   # [K] mean predictive entropy (nat) inside the predicted structure
+    voxels: np.ndarray                         # [K] int64: voxels of the predicted structure
+
+
+QUALITY_COLUMNS = ("class", "voxels", "dice_agreement", "iou_all", "volume_cv", "mean_entropy")
+
+
+def structure_agreement(counts, members):
+    """The label-free, structure-wise quality measures of Roy et al. 2019 (Bayesian QuickNAT) from the int64 counts
+    ``[K, 2 T + 4]`` that ``ops.tta_uncertainty`` accumulates over a volume (NumPy array or tensor; ``members`` = T; row k =
+    ``{V, ALL, ANY, HSUM, V_0 .. V_{T-1}, I_0 .. I_{T-1}}``, ``ops.UncertaintyLayout``), per class, in fp64:
+    ``dice_agreement = mean_t 2 I_t / (V_t + V)`` (each member against the consensus), ``iou_all = ALL / ANY``,
+    ``volume_cv = pstdev_t(V_t) / mean_t(V_t)``, ``mean_entropy = HSUM / 2^20 / V``, ``voxels = V``.  A quantity is ``nan`` where
+    its denominator is 0 (``dice_agreement``: where any member's is).  Pure host code; a device tensor is read back here."""
+    from ..ops import UNCERTAIN_ENTROPY_SCALE, UncertaintyLayout
+    lay = UncertaintyLayout(members)
+    if hasattr(counts, "detach"):
+        counts = counts.detach().cpu().numpy()
+    c = np.asarray(counts)
+    if c.dtype != np.int64:
+        raise TypeError(f"structure_agreement: counts must be int64, got {c.dtype}")
+    if c.ndim != 2 or c.shape[1] != lay.slots:
+        raise ValueError(f"structure_agreement: counts must be [K, 2 T + 4] = [K, {lay.slots}] for {members} members, got {c.shape}")
+    v = c[:, lay.V].astype(np.float64)
+    vt, it = lay.member_voxels(c).astype(np.float64), lay.member_overlap(c).astype(np.float64)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        ratio = lambda a, b: np.where(b != 0, a / b, np.nan)
+        dice = ratio(2.0 * it, vt + v[:, None]).mean(axis=1)
+        iou = ratio(c[:, lay.ALL].astype(np.float64), c[:, lay.ANY].astype(np.float64))
+        cv = ratio(vt.std(axis=1), vt.mean(axis=1))
+        ent = ratio(c[:, lay.HSUM].astype(np.float64) / UNCERTAIN_ENTROPY_SCALE, v)
+    return StructureAgreement(dice, iou, cv, ent, c[:, lay.V].copy())
+
+
+def format_quality_csv(quality, names=None):
+    """``quality.csv``: a header line (``QUALITY_COLUMNS``) and one line per class of a ``StructureAgreement``: the class (its
+    index, or ``names[k]``), the voxel count, then the four scores as '%.6f' (``nan`` as Python formats it)."""
+    k = len(quality.voxels)
+    if names is not None and len(names) != k:
+        raise ValueError(f"format_quality_csv: {len(names)} names for {k} classes")
+    lines = [",".join(QUALITY_COLUMNS)]
+    for i in range(k):
+        scores = (quality.dice_agreement[i], quality.iou_all[i], quality.volume_cv[i], quality.mean_entropy[i])
+        lines.append(",".join([str(i if names is None else names[i]), str(int(quality.voxels[i]))] + ["%.6f" % s for s in scores]))
+    return "\n".join(lines) + "\n"
 
 
 class Meter:

@@ -2882,6 +2882,40 @@ def tta_expand(img_u8, transforms):
     return out
 
 
+def _tta_members(what, members, transforms, classes):
+    """The checks ``tta_merge`` and ``tta_uncertainty`` share, all on the host: ``(members as a list, transforms, n, c, h, w, k)``."""
+    tr = tta_transforms(transforms)
+    try:
+        members = list(members)
+    except TypeError:
+        raise TypeError(f"{what}: members must be a sequence of tensors, got {type(members).__name__}") from None
+    for i, m in enumerate(members):
+        if not isinstance(m, torch.Tensor):
+            raise TypeError(f"{what}: member {i} must be a tensor, got {type(m).__name__}")
+        if m.dtype != torch.float32:
+            raise TypeError(f"{what}: member {i} must be float32, got {m.dtype}")
+    if not 1 <= len(members) <= TTA_MAX_MEMBERS:
+        raise ValueError(f"{what}: needs 1..{TTA_MAX_MEMBERS} members, got {len(members)}")
+    for i, m in enumerate(members):
+        if not m.is_cuda or m.device != members[0].device:
+            raise TypeError(f"{what}: member {i} must be on the first member's HIP device, got {m.device} (no CPU fallback)")
+    if len(tr) != len(members):
+        raise ValueError(f"{what}: {len(members)} members but {len(tr)} transforms")
+    if members[0].dim() != 4:
+        raise ValueError(f"{what}: expected NCHW logits, got shape {tuple(members[0].shape)}")
+    n, c, h, w = members[0].shape
+    for i, m in enumerate(members):
+        if tuple(m.shape) != (n, c, h, w):
+            raise ValueError(f"{what}: member {i} has shape {tuple(m.shape)}, member 0 {(n, c, h, w)}")
+    k = c if classes is None else int(classes)
+    if not 1 <= k <= min(c, TTA_MAX_CLASSES):
+        raise ValueError(f"{what}: classes must lie in 1..min(C, {TTA_MAX_CLASSES}), got {k} with C = {c}")
+    _tta_check_plane(what, tr, h, w)
+    if n > TTA_MAX_SLICES:
+        raise ValueError(f"{what}: at most {TTA_MAX_SLICES} slices, got {n}")
+    return members, tr, n, c, h, w, k
+
+
 def tta_merge(members, transforms, classes=None, want_conf=False, want_prob=False):
     """Test-time augmentation / ensembling in one pass (csrc/tta.hip).  ``members``: T logit tensors, logical NCHW ``[N, C, H, W]``
     fp32 in the NHWC memory the networks leave them in (read in place, each logit once; they are not stacked), member ``t`` being
@@ -2892,35 +2926,7 @@ def tta_merge(members, transforms, classes=None, want_conf=False, want_prob=Fals
     of that class, or None; ``prob`` fp32 ``[N, H, W, classes]`` or None.  Bitwise reproducible.  ``TypeError`` for wrong types
     or devices, ``ValueError`` for shapes, values or a quarter turn of a non-square slice, before the device is touched."""
     import ctypes
-    tr = tta_transforms(transforms)
-    try:
-        members = list(members)
-    except TypeError:
-        raise TypeError(f"tta_merge: members must be a sequence of tensors, got {type(members).__name__}") from None
-    for i, m in enumerate(members):
-        if not isinstance(m, torch.Tensor):
-            raise TypeError(f"tta_merge: member {i} must be a tensor, got {type(m).__name__}")
-        if m.dtype != torch.float32:
-            raise TypeError(f"tta_merge: member {i} must be float32, got {m.dtype}")
-    if not 1 <= len(members) <= TTA_MAX_MEMBERS:
-        raise ValueError(f"tta_merge: needs 1..{TTA_MAX_MEMBERS} members, got {len(members)}")
-    for i, m in enumerate(members):
-        if not m.is_cuda or m.device != members[0].device:
-            raise TypeError(f"tta_merge: member {i} must be on the first member's HIP device, got {m.device} (no CPU fallback)")
-    if len(tr) != len(members):
-        raise ValueError(f"tta_merge: {len(members)} members but {len(tr)} transforms")
-    if members[0].dim() != 4:
-        raise ValueError(f"tta_merge: expected NCHW logits, got shape {tuple(members[0].shape)}")
-    n, c, h, w = members[0].shape
-    for i, m in enumerate(members):
-        if tuple(m.shape) != (n, c, h, w):
-            raise ValueError(f"tta_merge: member {i} has shape {tuple(m.shape)}, member 0 {(n, c, h, w)}")
-    k = c if classes is None else int(classes)
-    if not 1 <= k <= min(c, TTA_MAX_CLASSES):
-        raise ValueError(f"tta_merge: classes must lie in 1..min(C, {TTA_MAX_CLASSES}), got {k} with C = {c}")
-    _tta_check_plane("tta_merge", tr, h, w)
-    if n > TTA_MAX_SLICES:
-        raise ValueError(f"tta_merge: at most {TTA_MAX_SLICES} slices, got {n}")
+    members, tr, n, c, h, w, k = _tta_members("tta_merge", members, transforms, classes)
     dev = members[0].device
     pred = torch.empty(n, h, w, dtype=torch.uint8, device=dev)
     conf = torch.empty(n, h, w, dtype=torch.float32, device=dev) if want_conf else None
@@ -2933,6 +2939,81 @@ def tta_merge(members, transforms, classes=None, want_conf=False, want_prob=Fals
     H.call("smsut_tta_merge", ctypes.addressof(ptrs), addr, pred, conf, prob, len(zs), n, h, w, c, k, _s())
     del keep, ptrs
     return pred, conf, prob
+
+
+# ------------------------------------------------------------------------------------------- uncertainty (csrc/uncertainty.hip)
+UNCERTAIN_ENTROPY_SCALE = 1 << 20                              # HSUM counts entropy in units of 2^-20 nat (csrc/uncertainty.hip)
+
+
+class UncertaintyLayout:
+    """Where ``tta_uncertainty`` keeps what in a row of its int64 ``counts [classes, 2 T + 4]`` (include/smsut_hip.h): columns
+    ``V`` (pixels predicted k), ``ALL`` (every member chose k), ``ANY`` (some member chose k), ``HSUM`` (the entropy of the pixels
+    predicted k, summed in units of 2^-20 nat); ``member_voxels`` (``V_t``: member t chose k) and ``member_overlap`` (``I_t``:
+    member t chose k and so did the prediction) are ``[classes, T]`` views of an array or tensor.  Pure host code."""
+    V, ALL, ANY, HSUM, FIXED = 0, 1, 2, 3, 4
+
+    def __init__(self, members):
+        if isinstance(members, bool) or not isinstance(members, int):
+            raise TypeError(f"UncertaintyLayout: members must be an int, got {type(members).__name__}")
+        if not 1 <= members <= TTA_MAX_MEMBERS:
+            raise ValueError(f"UncertaintyLayout: members must lie in 1..{TTA_MAX_MEMBERS}, got {members}")
+        self.members = members
+        self.slots = 2 * members + self.FIXED
+
+    def member_voxels(self, counts):
+        return counts[:, self.FIXED:self.FIXED + self.members]
+
+    def member_overlap(self, counts):
+        return counts[:, self.FIXED + self.members:self.slots]
+
+
+class Uncertainty(NamedTuple):
+    pred: torch.Tensor                         # uint8 [N, H, W]: tta_merge's prediction, bit for bit
+    conf: torch.Tensor                         # fp32 [N, H, W]: tta_merge's confidence, bit for bit
+    entropy: Optional[torch.Tensor]            # fp32 [N, H, W]: the entropy of the mean probabilities (nat)
+    mutual_info: Optional[torch.Tensor]        # fp32 [N, H, W]: that entropy minus the members' mean entropy, clamped at 0
+    votes: Optional[torch.Tensor]              # uint8 [N, H, W]: the members whose own label is the prediction
+
+
+def tta_uncertainty(members, transforms, classes=None, counts=None, want_maps=True):
+    """``tta_merge``'s pass with the uncertainty of its prediction (csrc/uncertainty.hip): the same members, transforms and
+    ``classes``, read the same way, once.  Returns ``Uncertainty(pred, conf, entropy, mutual_info, votes)``: ``pred`` / ``conf`` are
+    bitwise ``tta_merge``'s; ``entropy`` is H = -sum_k mean_k log(mean_k + 1e-6) of the averaged probabilities; ``mutual_info`` is
+    H minus the mean of the members' own entropies (BALD: large where the members contradict each other, not where all are unsure),
+    clamped at 0; ``votes`` counts the members whose own label -- the first maximum of their logits -- is ``pred``.  With
+    ``want_maps=False`` these three are None.  ``counts``: an int64 contiguous ``[classes, 2 T + 4]`` tensor on the members' device
+    that the call ADDS the per-class agreement counts into (``UncertaintyLayout``; ``misc.utils.structure_agreement`` turns them
+    into scores); the caller zeroes it once per volume.  Integers and per-pixel arithmetic only: bitwise reproducible.
+    ``TypeError`` for wrong types or devices, ``ValueError`` for shapes and values, before the device is touched."""
+    import ctypes
+    if counts is not None:
+        if not isinstance(counts, torch.Tensor):
+            raise TypeError(f"tta_uncertainty: counts must be a tensor, got {type(counts).__name__}")
+        if counts.dtype != torch.int64:
+            raise TypeError(f"tta_uncertainty: counts must be int64, got {counts.dtype}")
+    members, tr, n, c, h, w, k = _tta_members("tta_uncertainty", members, transforms, classes)
+    dev = members[0].device
+    if counts is not None:
+        if counts.device != dev:
+            raise TypeError(f"tta_uncertainty: counts must be on the members' device {dev}, got {counts.device}")
+        slots = UncertaintyLayout(len(tr)).slots
+        if tuple(counts.shape) != (k, slots) or not counts.is_contiguous():
+            raise ValueError(f"tta_uncertainty: counts must be a contiguous [{k}, {slots}] tensor ([classes, 2 T + 4]), got shape "
+                             f"{tuple(counts.shape)}, strides {tuple(counts.stride())}")
+    pred = torch.empty(n, h, w, dtype=torch.uint8, device=dev)
+    conf = torch.empty(n, h, w, dtype=torch.float32, device=dev)
+    entropy = torch.empty(n, h, w, dtype=torch.float32, device=dev) if want_maps else None
+    mutual = torch.empty(n, h, w, dtype=torch.float32, device=dev) if want_maps else None
+    votes = torch.empty(n, h, w, dtype=torch.uint8, device=dev) if want_maps else None
+    if n == 0:
+        return Uncertainty(pred, conf, entropy, mutual, votes)
+    zs = [nhwc(m.detach()) for m in members]                  # (a network's output already is NHWC: no copy)
+    ptrs = (ctypes.c_void_p * len(zs))(*[z.data_ptr() for z in zs])
+    keep, addr = _tta_host_ints(tr)
+    H.call("smsut_tta_uncertain", ctypes.addressof(ptrs), addr, pred, conf, entropy, mutual, votes, counts, len(zs), n, h, w, c, k,
+           _s())
+    del keep, ptrs
+    return Uncertainty(pred, conf, entropy, mutual, votes)
 
 
 # ------------------------------------------------------------------------------------------- calibration (test phase)

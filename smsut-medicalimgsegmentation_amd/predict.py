@@ -6,7 +6,9 @@
 the network sees the flipped / rotated copies of every slice (``ops.tta_expand``), and the class probabilities of all copies and all
 networks are averaged on the un-transformed grid in one pass (``ops.tta_merge``, csrc/tta.hip).  ``predict_volume`` wraps it between
 ``prepare_volume`` (raw scanner array -> processed grid) and ``restore_labels`` (labels back on the scanner's grid), with the test
-phase's 3-D connected-component cleanup in between.  Everything stays on the device; reading DICOM / NIfTI is the caller's business
+phase's 3-D connected-component cleanup in between.  ``uncertainty=True`` / ``--uncertainty`` adds, from the same pass over the
+member logits (``ops.tta_uncertainty``, csrc/uncertainty.hip), per-voxel entropy, mutual information and vote count and the label-free
+per-structure agreement scores (``misc.utils.structure_agreement``).  Everything stays on the device; reading DICOM / NIfTI is the caller's business
 (``.npy`` in and out).  The reference has no inference entry point: its only path through a trained network is the test phase, which
 needs a PNG tree, a split yaml and ground truth (trainer/baseTrainer.py:254-318).
 """
@@ -22,6 +24,7 @@ import torch
 from . import config as cfg
 from . import ops
 from .data_pprocess.volume import CROP_SIZE, NEW_SPACING, ResamplePlan, prepare_volume, restore_labels
+from .misc.utils import StructureAgreement, format_quality_csv, structure_agreement
 
 
 def group_plan(depth, batch_size):
@@ -134,6 +137,57 @@ class Predictor:
                         conf[start:start + count] = c
         return pred, conf
 
+    def predict_uncertain(self, image_u8):
+        """``predict_slices(confidence=True)`` with the uncertainty of the prediction (``ops.tta_uncertainty``): returns
+        ``UncertainSlices(pred, conf, entropy, mutual_info, votes, counts)``, the maps ``[D, H, W]`` on the device and ``counts``
+        the int64 ``[classes, 2 members + 4]`` agreement counts of the whole volume (``misc.utils.structure_agreement``).  Same
+        grouping, padding of the last group and trimming as ``predict_slices``; one ``tta_uncertainty`` call per group, also for
+        one member (whose entropy is then the network's own, with ``mutual_info`` 0 and ``votes`` 1); the padded slices never
+        reach it, so they count nowhere.  ``pred`` and ``conf`` are bitwise those of ``predict_slices(confidence=True)``."""
+        if not isinstance(image_u8, torch.Tensor) or image_u8.dtype != torch.uint8:
+            raise TypeError("predict_uncertain: image_u8 must be a uint8 tensor")
+        if not image_u8.is_cuda:
+            raise TypeError(f"predict_uncertain: image_u8 must be on a HIP device, got {image_u8.device} (no CPU fallback)")
+        if image_u8.dim() != 3 or image_u8.shape[0] < 1:
+            raise ValueError(f"predict_uncertain: expected [D >= 1, H, W] slices, got shape {tuple(image_u8.shape)}")
+        d, h, w = image_u8.shape
+        ops._tta_check_plane("predict_uncertain", self.transforms, h, w)
+        image_u8 = image_u8.contiguous()
+        for f in self.forwards:
+            for m in _modules_of(f):
+                m.eval()
+        bs, tr, dev = self.batch_size, self.transforms, image_u8.device
+        pred, votes = (torch.empty(d, h, w, dtype=torch.uint8, device=dev) for _ in range(2))
+        conf, entropy, mutual = (torch.empty(d, h, w, dtype=torch.float32, device=dev) for _ in range(3))
+        counts = None
+        with torch.no_grad():
+            for start, count, padding in self.plan(d):
+                x = ops.tta_expand(image_u8[start:start + count], tr)              # [T, count, 1, H, W]
+                if padding:
+                    full = torch.zeros(len(tr), bs, 1, h, w, dtype=torch.float32, device=dev)
+                    full[:, :count] = x
+                    x = full
+                outs = [f(x[t])[:count] for f in self.forwards for t in range(len(tr))]
+                k = outs[0].shape[1] if self.classes is None else self.classes
+                if counts is None:
+                    counts = torch.zeros(k, ops.UncertaintyLayout(self.members).slots, dtype=torch.int64, device=dev)
+                if any(s is not None for s in self.scales):
+                    scale = [s for s in self.scales for _ in range(len(tr))]
+                    outs = [o if s is None else o * s for o, s in zip(outs, scale)]
+                u = ops.tta_uncertainty(outs, tr * len(self.forwards), classes=k, counts=counts)
+                for whole, part in zip((pred, conf, entropy, mutual, votes), u):
+                    whole[start:start + count] = part
+        return UncertainSlices(pred, conf, entropy, mutual, votes, counts)
+
+
+class UncertainSlices(NamedTuple):
+    pred: torch.Tensor                         # uint8 [D, H, W]
+    conf: torch.Tensor                         # fp32 [D, H, W]: the mean probability of the predicted class
+    entropy: torch.Tensor                      # fp32 [D, H, W]: the entropy of the mean probabilities (nat)
+    mutual_info: torch.Tensor                  # fp32 [D, H, W]: the members' disagreement (BALD)
+    votes: torch.Tensor                        # uint8 [D, H, W]: the members whose own label is the prediction
+    counts: torch.Tensor                       # int64 [classes, 2 members + 4] (ops.UncertaintyLayout)
+
 
 class PredictResult(NamedTuple):
     labels: torch.Tensor                       # uint8: on the scanner's grid when restored, else the processed grid
@@ -142,16 +196,40 @@ class PredictResult(NamedTuple):
     plan: ResamplePlan
 
 
+class UncertainResult(NamedTuple):
+    labels: torch.Tensor                       # as PredictResult
+    labels_processed: torch.Tensor
+    confidence: Optional[torch.Tensor]
+    plan: ResamplePlan
+    entropy: torch.Tensor                      # fp32, processed grid: the entropy of the mean probabilities (nat)
+    mutual_info: torch.Tensor                  # fp32, processed grid: the members' disagreement (BALD)
+    votes: torch.Tensor                        # uint8, processed grid: the members whose own label is the prediction
+    quality: StructureAgreement                # per class, from the prediction BEFORE the cleanup (misc.utils.structure_agreement)
+    counts: torch.Tensor                       # int64 [classes, 2 members + 4], on the device: what ``quality`` was computed from
+
+
 def predict_volume(predictor, image, spacing, modality, cleanup=True, restore=True, confidence=False, new_spacing=NEW_SPACING,
-                   crop_size=CROP_SIZE):
+                   crop_size=CROP_SIZE, uncertainty=False):
     """Raw ``image`` ``[D, H, W]`` (NumPy array or device tensor, any real dtype) with voxel ``spacing`` ``(sz, sy, sx)`` ->
     ``PredictResult``: ``prepare_volume`` -> ``predictor.predict_slices`` -> the test phase's 3-D 18-neighbour connected-component
-    cleanup (``cleanup``) -> ``restore_labels`` onto the input's grid (``restore``).  The confidence stays on the processed grid."""
+    cleanup (``cleanup``) -> ``restore_labels`` onto the input's grid (``restore``).  The confidence stays on the processed grid.
+
+    ``uncertainty``: the slices go through ``predictor.predict_uncertain`` instead and the result is an ``UncertainResult``: the
+    same four fields (the same labels, bit for bit), the entropy, mutual-information and vote maps on the processed grid, and
+    ``quality``, the label-free per-structure scores.  The maps, the counts and ``quality`` describe the prediction BEFORE the
+    connected-component cleanup: the members' agreement on what the networks said, not on what the cleanup kept."""
     image_u8, _, plan = prepare_volume(image, None, spacing, modality, new_spacing=new_spacing, crop_size=crop_size)
-    pred, conf = predictor.predict_slices(image_u8, confidence=confidence)
+    if uncertainty:
+        u = predictor.predict_uncertain(image_u8)
+        pred, conf = u.pred, (u.conf if confidence else None)
+    else:
+        pred, conf = predictor.predict_slices(image_u8, confidence=confidence)
     if cleanup:
         pred = ops.cc_filter(pred, cfg.n_modal, per_slice=False)
     labels = restore_labels(pred, plan, tuple(image.shape)) if restore else pred
+    if uncertainty:
+        return UncertainResult(labels, pred, conf, plan, u.entropy, u.mutual_info, u.votes,
+                               structure_agreement(u.counts, predictor.members), u.counts)
     return PredictResult(labels, pred, conf, plan)
 
 
@@ -172,10 +250,13 @@ def make_parser():
     p.add_argument("--modality", required=True, help="'ct' windows to [-1000, 400]; any other name to the 0.05 / 99.5 percentiles")
     p.add_argument("--tta", default="none", choices=sorted(ops.TTA_SETS))
     p.add_argument("--confidence", action="store_true", help="also write confidence.npy (processed grid)")
+    p.add_argument("--uncertainty", action="store_true", help="also write entropy.npy, mutual_information.npy, votes.npy (processed "
+                   "grid) and quality.csv: label-free agreement scores per structure")
     p.add_argument("--temperature", default=None, help="temperature scaling of the probabilities: a number, or the path of the "
                    "temperature.txt that -p test writes with config.test_calibration")
     p.add_argument("--batch_size", type=int, default=None)
-    p.add_argument("--out", required=True, help="directory for labels.npy, labels_processed.npy (and confidence.npy)")
+    p.add_argument("--out", required=True, help="directory for labels.npy, labels_processed.npy (and confidence.npy, and the files of "
+                   "--uncertainty)")
     return p
 
 
@@ -192,6 +273,15 @@ def read_temperature(arg):
     if not words:
         raise ValueError(f"--temperature: {arg} is empty")
     return float(words[0])
+
+
+def write_uncertainty(out_dir, res):
+    """``--uncertainty``: the three maps of an ``UncertainResult`` as .npy and its ``quality`` as quality.csv"""
+    np.save(os.path.join(out_dir, "entropy.npy"), res.entropy.cpu().numpy())
+    np.save(os.path.join(out_dir, "mutual_information.npy"), res.mutual_info.cpu().numpy())
+    np.save(os.path.join(out_dir, "votes.npy"), res.votes.cpu().numpy())
+    with open(os.path.join(out_dir, "quality.csv"), "w") as f:
+        f.write(format_quality_csv(res.quality))
 
 
 def trainer_forwards(trainer):
@@ -212,12 +302,15 @@ def main(argv=None):
     predictor = Predictor(trainer_forwards(t), batch_size=args.batch_size, tta=args.tta, classes=cfg.n_label + 1,
                           temperature=read_temperature(args.temperature))
     image = np.load(args.image)
-    res = predict_volume(predictor, image, tuple(args.spacing), args.modality, confidence=args.confidence)
+    res = predict_volume(predictor, image, tuple(args.spacing), args.modality, confidence=args.confidence,
+                         uncertainty=args.uncertainty)
     os.makedirs(args.out, exist_ok=True)
     np.save(os.path.join(args.out, "labels.npy"), res.labels.cpu().numpy())
     np.save(os.path.join(args.out, "labels_processed.npy"), res.labels_processed.cpu().numpy())
     if args.confidence:
         np.save(os.path.join(args.out, "confidence.npy"), res.confidence.cpu().numpy())
+    if args.uncertainty:
+        write_uncertainty(args.out, res)
     return res
 
 
