@@ -10,6 +10,7 @@ MI355X-first differences (all opt-in or invisible to a caller of the reference A
   * TensorBoard / code snapshot / medpy are optional extras that are skipped when not installed.
 """
 import abc
+import argparse
 import logging
 import os
 import time
@@ -136,6 +137,56 @@ def sgd_step(optimizer):
 
 def make_adam(params, lr, betas, weight_decay):
     return torch.optim.Adam(params, lr, betas, weight_decay=weight_decay, fused=True)
+
+
+class LoaderCycle:
+    """``next()`` over ``loader`` forever: an exhausted pass is followed by a fresh ``iter(loader)``.  The first iterator is made
+    HERE, not at the first ``next()``: the in-turn samplers shuffle with the global ``random`` stream when they are iterated, so
+    the order in which a trainer builds its cycles (labelled, then unlabelled, before the loop) is part of the data order.  A
+    loader whose fresh pass yields nothing raises instead of spinning."""
+    _END = object()
+
+    def __init__(self, loader):
+        self.loader, self.it = loader, iter(loader)
+
+    def __iter__(self):
+        return self
+
+    def __next__(self):
+        batch = next(self.it, self._END)
+        if batch is self._END:
+            self.it = iter(self.loader)
+            batch = next(self.it, self._END)
+            if batch is self._END:
+                raise RuntimeError(f"{type(self.loader).__name__} yields no batch")
+        return batch
+
+
+def make_parser(phases, model_id_help=None):
+    """The five arguments every trainer module takes (reference uganConsisTrainer.py:308-315); ``phases``: its ``-p`` choices."""
+    p = argparse.ArgumentParser()
+    p.add_argument("-p", "--phase", type=str, choices=tuple(phases))
+    p.add_argument("-f", "--fold", type=int, default=0)
+    p.add_argument("-nm", "--expr_name", type=str)
+    p.add_argument("-i", "--model_id", type=str, help=model_id_help)
+    p.add_argument("-wh", "--which_ckpt", type=str, default="last")
+    return p
+
+
+def run_main(trainer_cls, parser, argv=None, extra=None, build_as=None):
+    """What the modules' ``main`` do: seed, build the trainer, then ``train`` -> ``fit('inTurn')`` and ``test`` -> ``load_model`` +
+    ``test('inTurn', expr_root/model_id)``.  ``extra``: {further phase: method name}, called like ``fit`` when the trainer is built
+    for training and like ``test`` (after ``load_model``) otherwise; ``build_as``: {phase: the phase the trainer is built with}."""
+    args = parser.parse_args(argv)
+    seed_all()
+    method = {"train": "fit", **(extra or {})}.get(args.phase, "test")
+    phase = (build_as or {}).get(args.phase, args.phase)
+    t = trainer_cls(phase, args)
+    if phase == "train":
+        getattr(t, method)("inTurn")
+    else:
+        t.load_model(args.model_id, args.which_ckpt)
+        getattr(t, method)("inTurn", t.expr_root + "/" + args.model_id)
 
 
 class BaseTrainer(abc.ABC):
@@ -321,10 +372,7 @@ class BaseTrainer(abc.ABC):
     def fit(self, loader_type="synthetic", max_epoch=None):
         lb, ul, test = self.get_loaders(loader_type)
         self.adopt_train_loaders(lb, ul)
-        keys_min = [f"loss_{i}" for i in range(cfg.n_modal)] + ["loss"]
-        keys_max = [f"dice_{i}" for i in range(cfg.n_modal)] + ["dice"]
-        train_meter = Meter(keys_min, [], alpha=cfg.exp_alpha)
-        test_meter = Meter(keys_min, keys_max, alpha=1.0)
+        train_meter, test_meter = self._meters()
         tic = time.time()
         for epoch in range(self.epoch, max_epoch or cfg.max_epoch):          # (self.epoch > 0 after resume())
             train_meter.reset_cur()
@@ -333,17 +381,28 @@ class BaseTrainer(abc.ABC):
             train_meter.update_cur()
             self.info("[TRN] Epoch: %d/%d, elapsed: %.2fs,%s" % (epoch, cfg.max_epoch, time.time() - tic, train_meter))
             tic = time.time()
-            test_meter.reset_cur()
-            dices = self._validation_dices(test, test_meter)
-            test_meter.accumulate(dices, {k: 1.0 for k in dices})
-            test_meter.update_cur()
-            self.info("[TST] Epoch: %d/%d, elapsed: %.2fs,%s" % (epoch, cfg.max_epoch, time.time() - tic, test_meter))
-            # save_model is collective under DP (per-rank train state): rank 0 decides, every rank follows
-            best = self._agree(self.model_idx is not None and test_meter.cur_values["dice"] >= test_meter.best_values["dice"])
-            if best:
+            if self._validate(test, test_meter, "", epoch, cfg.max_epoch, tic):
                 self.save_model(prefix="best")
         if self._agree(self.model_idx is not None):
             self.save_model(prefix="last")
+
+    @staticmethod
+    def _meters():
+        """(train meter, test meter) of a ``fit``: per-modality losses, and for the test meter the Dice values too."""
+        keys_min = [f"loss_{i}" for i in range(cfg.n_modal)] + ["loss"]
+        keys_max = [f"dice_{i}" for i in range(cfg.n_modal)] + ["dice"]
+        return Meter(keys_min, [], alpha=cfg.exp_alpha), Meter(keys_min, keys_max, alpha=1.0)
+
+    def _validate(self, test, test_meter, tag, epoch, n_epochs, tic):
+        """The validation block of an epoch: one pass over ``test`` into ``test_meter``, the ``[TST]`` line, and whether this
+        epoch's Dice is the best so far.  save_model is collective under DP (per-rank train state): rank 0 decides, every rank
+        follows."""
+        test_meter.reset_cur()
+        dices = self._validation_dices(test, test_meter)
+        test_meter.accumulate(dices, {k: 1.0 for k in dices})
+        test_meter.update_cur()
+        self.info("[TST] %sEpoch: %d/%d, elapsed: %.2fs,%s" % (tag, epoch, n_epochs, time.time() - tic, test_meter))
+        return self._agree(self.model_idx is not None and test_meter.cur_values["dice"] >= test_meter.best_values["dice"])
 
     def _agree(self, flag):
         """Rank 0's decision, on every rank (validation data / run directories exist per rank or on rank 0 only)."""
@@ -381,30 +440,81 @@ class BaseTrainer(abc.ABC):
     def train_epoch(self, lb_loader, ul_loader, meter):
         ...
 
+    def lb_ul_epoch(self, lb_loader, ul_loader, meter):
+        """The ``train_epoch`` of the trainers whose iteration takes [labelled | unlabelled] slices and the labels (meanTeacher,
+        dtc, crossPse): ``train_iteration(img, msk)`` on a batch of each loader, ``_meter_step`` when a meter was passed,
+        ``_log_step`` every ``log_step`` iterations."""
+        self.net.train()
+        lb, ul = LoaderCycle(lb_loader), LoaderCycle(ul_loader)
+        for i in range(cfg.num_iter_per_epoch):
+            img1, msk, mdl1, _ = next(lb)
+            img2, _, _, _ = next(ul)
+            img = torch.cat([img1.to(self.device, non_blocking=True), img2.to(self.device, non_blocking=True)], 0)
+            scal = self.train_iteration(img, msk.to(self.device, non_blocking=True))
+            if meter is not None:
+                self._meter_step(meter, scal, mdl1[0].item(), img.size(0))
+            if (i + 1) % self.log_step == 0:
+                self._log_step(i, scal)
+
+    def _meter_step(self, meter, scal, modal, n):
+        """``lb_ul_epoch``: what of an iteration's scalars the meter counts -- the first one, the segmentation loss."""
+        meter.accumulate(*meter.collect_loss_by(scal[0].item(), modal, n))
+
+    def set_poly_lr(self, *optimizers):
+        """The tail of every training step: the poly learning rate of the current ``iter`` into all of ``optimizers``."""
+        lr_ = self.poly_lr()
+        for opt in optimizers:
+            for g in opt.param_groups:
+                g["lr"] = lr_
+
+    def build_teacher(self, factory):
+        """The EMA teacher of meanTeacher and CoraNet: ``factory()`` once more -- an independent random init, never a copy of the
+        student (reference meanTeacherTrainer.py:53, coraNetTrainer.py:157-161) -- without gradients, broadcast from rank 0."""
+        ema = factory()
+        for p in ema.parameters():
+            p.requires_grad_(False)
+        parallel.broadcast_parameters(ema, self.group)
+        return ema
+
+    def ema_alpha(self):
+        """alpha of ``ema = alpha * ema + (1 - alpha) * student``: 0 for the first 100 iterations, then 1 - 1 / (iter + 1) up to
+        ``ema_decay``."""
+        return 0 if self.iter < 100 else min(1 - 1 / (self.iter + 1), self.ema_decay)
+
     def _forward_eval(self, img):
         return self.net(img)
 
     # ------------------------------------------------------------------ calibration of the test phase (cfg.test_calibration)
     _calibration = None            # a misc.utils.CalibrationReport while ``test`` runs its validation loop with the flag on
 
-    def _eval_classes(self, out):
-        """The leading channels of ``out`` that are classes, or None for all of them (coraNetTrainer: head 0)."""
-        return None
-
     def _calibration_feed(self, out, msk, mdl):
-        """The validation loops' hook: one ``ops.calibration_stats`` call on the batch they hold (``msk`` on the device), counted
+        """The evaluation loop's hook: one ``ops.calibration_stats`` call on the batch it holds (``msk`` on the device), counted
         for the batch's modality ``mdl[0]`` as the meter counts its loss; nothing is read back.  Nothing happens outside a
         ``test`` with ``cfg.test_calibration``."""
         if self._calibration is not None:
             self._calibration.update(out, msk, int(mdl[0].item()), self._eval_classes(out))
 
-    def validate_epoch(self, loader, npys, meter=None, save_path=None):
-        """baseTrainer.py:207-244 / uganShp0Trainer.py:250-287: no-grad inference, last batch padded to
-        cfg.batch_size, on-GPU argmax, volume assembly by name 'm_pid_z'."""
+    # ------------------------------------------------------------------ the evaluation loop and its three hooks
+    def _eval_classes(self, out):
+        """The leading channels of ``out`` that are classes, or None for all of them (coraNetTrainer: head 0)."""
+        return None
+
+    def _eval_loss(self, out, msk):
+        """The validation loss of one batch (coraNetTrainer: the three-head supervised loss)."""
+        return self.loss(out, msk)
+
+    def _eval_pred(self, out):
+        """The host path's prediction map of one batch (coraNetTrainer: the argmax of head 0)."""
+        return ops.argmax_channels(out)
+
+    def _eval_batches(self, loader):
+        """What both validation paths do with a batch before they score it: a short batch is padded with zero images to
+        cfg.batch_size, ``_forward_eval`` without gradients, the logits cropped back, the labels moved to the device, the
+        calibration fed.  Yields ``(logits, device labels, the loader's host modality ids, its names, the real batch size b, the
+        padded size the meter counts)``."""
         self.net.eval()
-        prd, n_prd = {k: np.zeros(v.shape, dtype=v.dtype) for k, v in npys.items()}, 0
-        with torch.no_grad():
-            for img, msk, mdl, inm in loader:
+        for img, msk, mdl, inm in loader:
+            with torch.no_grad():                            # (left again before the ``yield``: the consumer sets its own mode)
                 b, c, h, w = img.shape
                 img = img.to(self.device)
                 if b != cfg.batch_size:
@@ -413,12 +523,20 @@ class BaseTrainer(abc.ABC):
                 if b != cfg.batch_size:
                     out = out[:b]
                 msk = msk.to(self.device)
-                loss = self.loss(out, msk)
-                if meter is not None:
-                    v, n = meter.collect_loss_by(loss.item(), mdl[0].item(), img.size(0))
-                    meter.accumulate(v, n)
                 self._calibration_feed(out, msk, mdl)
-                pred = ops.argmax_channels(out).cpu().numpy()
+            yield out, msk, mdl, inm, b, img.size(0)
+
+    def validate_epoch(self, loader, npys, meter=None, save_path=None):
+        """baseTrainer.py:207-244 / uganShp0Trainer.py:250-287: no-grad inference, last batch padded to
+        cfg.batch_size, on-GPU argmax, volume assembly by name 'm_pid_z'."""
+        prd, n_prd = {k: np.zeros(v.shape, dtype=v.dtype) for k, v in npys.items()}, 0
+        with torch.no_grad():
+            for out, msk, mdl, inm, b, padded in self._eval_batches(loader):
+                loss = self._eval_loss(out, msk)
+                if meter is not None:
+                    v, n = meter.collect_loss_by(loss.item(), mdl[0].item(), padded)
+                    meter.accumulate(v, n)
+                pred = self._eval_pred(out).cpu().numpy()
                 for i in range(b):
                     m, pid, z = inm[i].split("_")
                     prd[f"{m}_{pid}"][int(z)] = pred[i]
@@ -432,11 +550,6 @@ class BaseTrainer(abc.ABC):
         return d
 
     # ------------------------------------------------------------------ validation on the device (cfg.validate_on_device)
-    def _eval_loss(self, out, msk):
-        """``(validation loss of one batch, class count of the prediction or None for all channels)``: the one thing a
-        trainer with another validation loss or head layout overrides (coraNetTrainer)."""
-        return self.loss(out, msk), None
-
     def validate_epoch_device(self, loader, meter=None, keep_volumes=False):
         """``validate_epoch`` without the host in the loop: the same batches, the same zero-padding of a short batch to
         cfg.batch_size and crop back, the same loss -- but the loss scalar stays on the device, prediction and Dice counting
@@ -455,26 +568,16 @@ class BaseTrainer(abc.ABC):
         equal integers.  Slices are paired with their labels per batch, not by volume index: a repeated name raises
         ``ValueError`` here, where the host path would overwrite the earlier slice."""
         from ..misc.utils import DiceCounter
-        self.net.eval()
         counter, n_prd = DiceCounter(), 0
         losses, meter_args = [], []
         preds, gts, where, lab_range = [], [], {}, None
         with torch.no_grad():
-            for img, msk, mdl, inm in loader:
-                b, c, h, w = img.shape
-                img = img.to(self.device)
-                if b != cfg.batch_size:
-                    img = torch.cat([img, torch.zeros(cfg.batch_size - b, c, h, w, device=self.device)], 0)
-                out = self._forward_eval(img)
-                if b != cfg.batch_size:
-                    out = out[:b]
-                msk = msk.to(self.device)
-                loss, classes = self._eval_loss(out, msk)
+            for out, msk, mdl, inm, b, padded in self._eval_batches(loader):
+                loss = self._eval_loss(out, msk)
                 if meter is not None:
                     losses.append(loss.detach().reshape(-1)[0])
-                    meter_args.append((mdl[0].item(), img.size(0)))
-                pred = counter.update(out, msk, inm[:b], classes=classes, want_pred=keep_volumes)
-                self._calibration_feed(out, msk, mdl)
+                    meter_args.append((mdl[0].item(), padded))
+                pred = counter.update(out, msk, inm[:b], classes=self._eval_classes(out), want_pred=keep_volumes)
                 if keep_volumes:
                     for i in range(b):
                         m, pid, z = inm[i].split("_")

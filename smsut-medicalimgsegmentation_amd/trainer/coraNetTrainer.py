@@ -4,7 +4,6 @@ loss; training adds, on slices pseudo-labelled by the student itself, a Dice + m
 ("certain") and a softmax-MSE consistency with the teacher where they do not ("uncertain").  The convolutional path is the U-Net's;
 everything after the logits runs in the fused head kernels of csrc/coranet.hip (``ops.cora_sup_loss``, ``ops.cora_semi_loss``,
 ``ops.cora_pseudo``, ``ops.ema_update``): no head is ever concatenated out of the logits."""
-import argparse
 import time
 from os.path import join as pjoin
 
@@ -13,9 +12,9 @@ import torch
 
 from .. import config as cfg
 from .. import ops, parallel
-from ..misc.utils import Meter
 from ..network.unet import UNet
-from .baseTrainer import seed_all, BaseTrainer, make_sgd, sgd_step
+from . import baseTrainer
+from .baseTrainer import BaseTrainer, LoaderCycle, make_sgd, run_main, sgd_step
 
 SCALARS = ("supervised", "dice_ce", "con", "rad", "certain", "uncertain")
 
@@ -57,18 +56,14 @@ class coraNetTrainer(BaseTrainer):
         vec = lambda pair: torch.tensor(cfg.class_weights(pair), dtype=torch.float32, device=self.device)
         self.w_con, self.w_rad = vec(cfg.w_con), vec(cfg.w_rad)
         if self.phase == "train":
-            # an independent random init for the teacher, never a copy of the student (:157-161)
-            self.ema = mk()
-            for p in self.ema.parameters():
-                p.requires_grad_(False)
-            parallel.broadcast_parameters(self.ema, self.group)
+            self.ema = self.build_teacher(mk)
             self.optimizer = make_sgd(self.net.parameters(), cfg.lr, 0.9, cfg.weight_decay)
             self.reducer = parallel.GradAllReducer(self.net.parameters(), self.group)
 
     # ------------------------------------------------------------------ teacher
     def update_ema_variable(self):
         """:168-174 -- ema = alpha * ema + (1 - alpha) * student in one launch; alpha = 0 for the first 100 iterations."""
-        self.alpha = 0 if self.iter < 100 else min(1 - 1 / (self.iter + 1), self.ema_decay)
+        self.alpha = self.ema_alpha()
         ops.ema_update(self.ema.parameters(), self.net.parameters(), self.alpha)
 
     def save_ema_model(self, prefix):
@@ -134,9 +129,7 @@ class coraNetTrainer(BaseTrainer):
         self.reducer.reduce()
         sgd_step(self.optimizer)
         self.update_ema_variable()
-        lr_ = self.poly_lr()
-        for g in self.optimizer.param_groups:
-            g["lr"] = lr_
+        self.set_poly_lr(self.optimizer)
         self.iter += 1
         return torch.cat([sup.detach(), semi.detach()])
 
@@ -164,19 +157,11 @@ class coraNetTrainer(BaseTrainer):
         return PseudoBatches(img, plab, mask, lab, mdl, bs), dice
 
     # ------------------------------------------------------------------ epochs
-    @staticmethod
-    def _next(itr, loader):
-        try:
-            return next(itr), itr
-        except StopIteration:
-            itr = iter(loader)
-            return next(itr), itr
-
     def pre_epoch(self, lb_loader, ul_loader, meter):
         self.net.train()
-        lb_itr = iter(lb_loader)
+        lb = LoaderCycle(lb_loader)
         for i in range(cfg.num_iter_per_epoch):
-            (img1, msk, mdl1, _), lb_itr = self._next(lb_itr, lb_loader)
+            img1, msk, mdl1, _ = next(lb)
             scal = self.pretrain_iteration(img1.to(self.device, non_blocking=True), msk.to(self.device, non_blocking=True))
             if meter is not None:
                 v, n = meter.collect_loss_by(scal[0].item(), mdl1[0].item(), 2 * img1.size(0))
@@ -191,10 +176,10 @@ class coraNetTrainer(BaseTrainer):
         if new_loader is None:
             raise RuntimeError("coraNetTrainer.train_epoch needs the pseudo-labelled batches of pred_unlabel()")
         self.net.train(); self.ema.train()
-        lb_itr, pse_itr = iter(lb_loader), iter(new_loader)
+        lb, pse = LoaderCycle(lb_loader), LoaderCycle(new_loader)
         for i in range(cfg.num_iter_per_epoch):
-            (img1, msk, mdl1, _), lb_itr = self._next(lb_itr, lb_loader)
-            (img2, plab, mask, _, _), pse_itr = self._next(pse_itr, new_loader)
+            img1, msk, mdl1, _ = next(lb)
+            img2, plab, mask, _, _ = next(pse)
             scal = self.train_iteration(img1.to(self.device, non_blocking=True), msk.to(self.device, non_blocking=True), img2, plab, mask)
             if meter is not None:
                 s = scal.tolist()
@@ -204,19 +189,6 @@ class coraNetTrainer(BaseTrainer):
                 s = scal.tolist()
                 self.info("Iter %d, global_iter: %d, supervised_loss: %.4f, certain_loss: %.4f, uncertain_loss: %f"
                           % (i, self.iter, s[0], s[4], s[5]))
-
-    def _meters(self):
-        keys_min = [f"loss_{i}" for i in range(cfg.n_modal)] + ["loss"]
-        keys_max = [f"dice_{i}" for i in range(cfg.n_modal)] + ["dice"]
-        return Meter(keys_min, [], alpha=cfg.exp_alpha), Meter(keys_min, keys_max, alpha=1.0)
-
-    def _validate(self, test, test_meter, tag, epoch, n_epochs, tic):
-        test_meter.reset_cur()
-        dices = self._validation_dices(test, test_meter)
-        test_meter.accumulate(dices, {k: 1.0 for k in dices})
-        test_meter.update_cur()
-        self.info("[TST] %sEpoch: %d/%d, elapsed: %.2fs,%s" % (tag, epoch, n_epochs, time.time() - tic, test_meter))
-        return self._agree(self.model_idx is not None and test_meter.cur_values["dice"] >= test_meter.best_values["dice"])
 
     def prefit(self, loader_type="synthetic", max_epoch=None):
         """:526-602 -- ``cfg.pre_epoch`` epochs of the supervised three-head loss; the best validation Dice writes ``pre_best`` /
@@ -267,38 +239,16 @@ class coraNetTrainer(BaseTrainer):
         if self._agree(self.model_idx is not None):
             self.save_model(prefix="last")
 
-    def validate_epoch(self, loader, npys, meter=None, save_path=None):
-        """:692-744 -- ``BaseTrainer.validate_epoch`` with the three-head supervised loss and the argmax of head 0."""
-        self.net.eval()
-        prd, n_prd = {k: np.zeros(v.shape, dtype=v.dtype) for k, v in npys.items()}, 0
-        with torch.no_grad():
-            for img, msk, mdl, inm in loader:
-                b, c, h, w = img.shape
-                img = img.to(self.device)
-                if b != cfg.batch_size:
-                    img = torch.cat([img, torch.zeros(cfg.batch_size - b, c, h, w, device=self.device)], 0)
-                out = self._forward_eval(img)
-                if b != cfg.batch_size:
-                    out = out[:b]
-                msk = msk.to(self.device)
-                loss = self.sup_loss(out, msk)[0]
-                if meter is not None:
-                    v, n = meter.collect_loss_by(loss.item(), mdl[0].item(), img.size(0))
-                    meter.accumulate(v, n)
-                self._calibration_feed(out, msk, mdl)
-                pred = ops.cora_pseudo(out)[0].cpu().numpy()
-                for i in range(b):
-                    m, pid, z = inm[i].split("_")
-                    prd[f"{m}_{pid}"][int(z)] = pred[i]
-                    n_prd += 1
-        return n_prd, prd
-
+    # ------------------------------------------------------------------ evaluation: the three-head loss, head 0 predicts (:692-744)
     def _eval_loss(self, out, msk):
-        """``validate_epoch_device``'s hook: the three-head supervised loss, and head 0 (channels 0 .. L of the 3L+1) predicts."""
-        return self.sup_loss(out, msk)[0], (out.shape[1] - 1) // 3 + 1
+        return self.sup_loss(out, msk)[0]
 
     def _eval_classes(self, out):
+        """Head 0 is channels 0 .. L of the 3L+1."""
         return (out.shape[1] - 1) // 3 + 1
+
+    def _eval_pred(self, out):
+        return ops.cora_pseudo(out)[0]
 
     def save_pseudo(self, loader_type, expr_root):
         """``-p pseudo``: pseudo labels and certainty masks of the unlabelled slices as ``pseudo/{plab,mask}.npy`` (uint8)."""
@@ -313,31 +263,13 @@ class coraNetTrainer(BaseTrainer):
 
 
 def make_parser():
-    p = argparse.ArgumentParser()
-    p.add_argument("-p", "--phase", type=str, choices=("pretrain", "train", "test", "pseudo"))
-    p.add_argument("-f", "--fold", type=int, default=0)
-    p.add_argument("-nm", "--expr_name", type=str)
-    p.add_argument("-i", "--model_id", type=str, help="run to load: pre_best / pre_ema_best for train, --which_ckpt for test / pseudo")
-    p.add_argument("-wh", "--which_ckpt", type=str, default="last")
-    return p
+    return baseTrainer.make_parser(("pretrain", "train", "test", "pseudo"),
+                                   model_id_help="run to load: pre_best / pre_ema_best for train, --which_ckpt for test / pseudo")
 
 
 def main(argv=None):
-    args = make_parser().parse_args(argv)
-    seed_all()
     # the reference's main has its prefit() call commented out (:764): the phase name `pretrain` is ours; it builds the same trainer
-    t = coraNetTrainer("train" if args.phase == "pretrain" else args.phase, args)
-    if args.phase == "pretrain":
-        t.prefit("inTurn")
-    elif args.phase == "train":
-        t.fit("inTurn")
-    else:
-        t.load_model(args.model_id, args.which_ckpt)
-        root = t.expr_root + "/" + args.model_id
-        if args.phase == "test":
-            t.test("inTurn", root)
-        else:
-            t.save_pseudo("inTurn", root)
+    run_main(coraNetTrainer, make_parser(), argv, extra={"pretrain": "prefit", "pseudo": "save_pseudo"}, build_as={"pretrain": "train"})
 
 
 if __name__ == "__main__":

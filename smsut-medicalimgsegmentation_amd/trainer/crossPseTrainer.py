@@ -1,16 +1,12 @@
 """``crossPseTrainer`` (reference trainer/crossPseTrainer.py:38-148): two U-Nets supervising each other with
 argmax pseudo labels on the unlabeled half (cross pseudo supervision), DiceCE everywhere, two SGDs + poly LR.
 Pure reuse of the U-Net kernels plus ``ops.argmax_channels``."""
-import argparse
-import random
-
-import numpy as np
 import torch
 
 from .. import config as cfg
 from .. import ops, parallel
 from ..network.unet import UNet
-from .baseTrainer import seed_all, BaseTrainer, make_sgd
+from .baseTrainer import BaseTrainer, make_parser, make_sgd, run_main
 
 
 class crossPseTrainer(BaseTrainer):
@@ -49,51 +45,26 @@ class crossPseTrainer(BaseTrainer):
             total.backward()
         self.reducer1.reduce(); self.reducer2.reduce()
         self.optimizer1.step(); self.optimizer2.step()
-        lr_ = self.poly_lr()
-        for g in list(self.optimizer1.param_groups) + list(self.optimizer2.param_groups):
-            g["lr"] = lr_
+        self.set_poly_lr(self.optimizer1, self.optimizer2)
         self.iter += 1
         return torch.stack([t.detach() for t in (s1, s2, semi1, semi2)])
 
     def train_epoch(self, lb_loader, ul_loader, meter):
-        self.net.train(); self.net2.train()
-        lb_itr, ul_itr = iter(lb_loader), iter(ul_loader)
-        for i in range(cfg.num_iter_per_epoch):
-            try:
-                img1, msk, mdl1, _ = next(lb_itr)
-            except StopIteration:
-                lb_itr = iter(lb_loader); img1, msk, mdl1, _ = next(lb_itr)
-            try:
-                img2, _, _, _ = next(ul_itr)
-            except StopIteration:
-                ul_itr = iter(ul_loader); img2, _, _, _ = next(ul_itr)
-            img = torch.cat([img1.to(self.device, non_blocking=True), img2.to(self.device, non_blocking=True)], 0)
-            scal = self.train_iteration(img, msk.to(self.device, non_blocking=True))
-            if meter is not None:
-                vals = scal.tolist()
-                for k in (0, 1):                                                              # :112-120: both nets are metered
-                    v, n = meter.collect_loss_by(vals[k], mdl1[0].item(), img.size(0))
-                    meter.accumulate(v, n)
-            if (i + 1) % self.log_step == 0:
-                self.info("Iter %d, global_iter: %d, crossPse1_loss: %.4f, crossPse2_loss: %.4f, seg1_loss: %.4f, seg2_loss: %.4f"
-                          % (i, self.iter, scal[2].item(), scal[3].item(), scal[0].item(), scal[1].item()))
+        self.net2.train()
+        self.lb_ul_epoch(lb_loader, ul_loader, meter)
+
+    def _meter_step(self, meter, scal, modal, n):
+        vals = scal.tolist()
+        for k in (0, 1):                                                                      # :112-120: both nets are metered
+            meter.accumulate(*meter.collect_loss_by(vals[k], modal, n))
+
+    def _log_step(self, i, scal):
+        self.info("Iter %d, global_iter: %d, crossPse1_loss: %.4f, crossPse2_loss: %.4f, seg1_loss: %.4f, seg2_loss: %.4f"
+                  % (i, self.iter, scal[2].item(), scal[3].item(), scal[0].item(), scal[1].item()))
 
 
 def main(argv=None):
-    p = argparse.ArgumentParser()
-    p.add_argument("-p", "--phase", type=str, choices=("train", "test"))
-    p.add_argument("-f", "--fold", type=int, default=0)
-    p.add_argument("-nm", "--expr_name", type=str)
-    p.add_argument("-i", "--model_id", type=str)
-    p.add_argument("-wh", "--which_ckpt", type=str, default="last")
-    args = p.parse_args(argv)
-    seed_all()
-    t = crossPseTrainer(args.phase, args)
-    if args.phase == "train":
-        t.fit("inTurn")
-    else:
-        t.load_model(args.model_id, args.which_ckpt)
-        t.test("inTurn", t.expr_root + "/" + args.model_id)
+    run_main(crossPseTrainer, make_parser(("train", "test")), argv)
 
 
 if __name__ == "__main__":

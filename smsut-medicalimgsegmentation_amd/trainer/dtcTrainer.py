@@ -5,14 +5,12 @@ the consistency ``mean((sigmoid(-k * tanh_out) - softmax(logits)) ** 2)`` betwee
 The signed distance maps are recomputed every iteration from the (augmented) labels ON THE DEVICE (``ops.signed_distance_map``,
 csrc/dtc.hip) -- the published code does that with scipy on the host -- and both DTC terms with their gradients come from the fused
 ``ops.dtc_loss``.  SGD + poly LR as the sibling baselines."""
-import argparse
-
 import torch
 
 from .. import config as cfg
 from .. import ops, parallel
 from ..network.dtc import UNet
-from .baseTrainer import seed_all, BaseTrainer, make_sgd, sgd_step
+from .baseTrainer import BaseTrainer, make_parser, make_sgd, run_main, sgd_step
 
 
 class dtcTrainer(BaseTrainer):
@@ -51,54 +49,27 @@ class dtcTrainer(BaseTrainer):
             total.backward()
         self.reducer.reduce()
         sgd_step(self.optimizer)
-        lr_ = self.poly_lr()
-        for g in self.optimizer.param_groups:
-            g["lr"] = lr_
+        self.set_poly_lr(self.optimizer)
         self.iter += 1
         return torch.cat([seg.detach().reshape(1), dtc.detach()])
 
-    def train_epoch(self, lb_loader, ul_loader, meter):
-        self.net.train()
-        lb_itr, ul_itr = iter(lb_loader), iter(ul_loader)
-        for i in range(cfg.num_iter_per_epoch):
-            try:
-                img1, msk, mdl1, _ = next(lb_itr)
-            except StopIteration:
-                lb_itr = iter(lb_loader); img1, msk, mdl1, _ = next(lb_itr)
-            try:
-                img2, _, _, _ = next(ul_itr)
-            except StopIteration:
-                ul_itr = iter(ul_loader); img2, _, _, _ = next(ul_itr)
-            img = torch.cat([img1.to(self.device, non_blocking=True), img2.to(self.device, non_blocking=True)], 0)
-            scal = self.train_iteration(img, msk.to(self.device, non_blocking=True))
-            if meter is not None:
-                v, n = meter.collect_loss_by(scal[0].item(), mdl1[0].item(), img.size(0))
-                meter.accumulate(v, n)
-                # the host has just waited for the scalars, so reading the bad-label word costs no extra wait: a label outside
-                # [0, C) raises here.  A caller that passes no meter never waits for the device in this loop and is NOT checked
-                # (such a pixel then simply belongs to no class); it can call ops.sdf_check() itself wherever it synchronises.
-                ops.sdf_check(self.device)
-            if (i + 1) % self.log_step == 0:
-                s = scal.tolist()
-                self.info("Iter %d, global_iter: %d, seg_loss: %.4f, sdf_loss: %.4f, consistency_loss: %.4f"
-                          % (i, self.iter, s[0], s[1], s[2]))
+    train_epoch = BaseTrainer.lb_ul_epoch
+
+    def _meter_step(self, meter, scal, modal, n):
+        super()._meter_step(meter, scal, modal, n)
+        # the host has just waited for the scalars, so reading the bad-label word costs no extra wait: a label outside
+        # [0, C) raises here.  A caller that passes no meter never waits for the device in this loop and is NOT checked
+        # (such a pixel then simply belongs to no class); it can call ops.sdf_check() itself wherever it synchronises.
+        ops.sdf_check(self.device)
+
+    def _log_step(self, i, scal):
+        s = scal.tolist()
+        self.info("Iter %d, global_iter: %d, seg_loss: %.4f, sdf_loss: %.4f, consistency_loss: %.4f"
+                  % (i, self.iter, s[0], s[1], s[2]))
 
 
 def main(argv=None):
-    p = argparse.ArgumentParser()
-    p.add_argument("-p", "--phase", type=str, choices=("train", "test"))
-    p.add_argument("-f", "--fold", type=int, default=0)
-    p.add_argument("-nm", "--expr_name", type=str)
-    p.add_argument("-i", "--model_id", type=str)
-    p.add_argument("-wh", "--which_ckpt", type=str, default="last")
-    args = p.parse_args(argv)
-    seed_all()
-    t = dtcTrainer(args.phase, args)
-    if args.phase == "train":
-        t.fit("inTurn")
-    else:
-        t.load_model(args.model_id, args.which_ckpt)
-        t.test("inTurn", t.expr_root + "/" + args.model_id)
+    run_main(dtcTrainer, make_parser(("train", "test")), argv)
 
 
 if __name__ == "__main__":

@@ -12,18 +12,15 @@ MI355X-first choices that do not change the arithmetic:
     (the reference does 11 ``.item()`` syncs per iteration);
   * RNG-dependent inputs (target modality, alpha ~ randn, patch ids ~ randperm) may be passed in for replay.
 """
-import argparse
 import os
 import random
 import time
-from os.path import join as pjoin
 
-import numpy as np
 import torch
 
 from .. import config as cfg
 from .. import graphs, ops
-from .baseTrainer import seed_all, sgd_step
+from .baseTrainer import LoaderCycle, make_parser, run_main, sgd_step
 from .uganShp0Trainer import UGANShp0Trainer
 
 SCALARS = ("D_real", "D_fake", "D_cls", "D_gp", "G_fake", "G_rec", "G_cls", "G_seg", "G_semi", "G_nce")
@@ -586,29 +583,21 @@ class UGANConsisTrainer(UGANShp0Trainer):
         if self._probe:
             self._finite_probe("G.step", list(self.net.named_parameters()))
 
-        lr_ = self.poly_lr()                                                                   # :198-202
-        for grp in list(self.optimizer.param_groups) + list(self.d_optimizer.param_groups):
-            grp["lr"] = lr_
+        self.set_poly_lr(self.optimizer, self.d_optimizer)                                     # :198-202
         self.iter += 1
         self._eager_done = True
         return torch.cat([d_scal, g_scal])
 
     def train_epoch(self, lb_loader, ul_loader, meter):
         self.net.train(); self.D.train()
-        lb_itr, ul_itr = iter(lb_loader), iter(ul_loader)
+        lb, ul = LoaderCycle(lb_loader), LoaderCycle(ul_loader)
         tic = time.time()
         from ..misc.utils import ScalarFetcher
         fetch = ScalarFetcher(len(SCALARS), self.device)
         try:
             for i in range(self.n_critic * cfg.num_iter_per_epoch):
-                try:
-                    x1, y_real, mo1, _ = next(lb_itr)
-                except StopIteration:
-                    lb_itr = iter(lb_loader); x1, y_real, mo1, _ = next(lb_itr)
-                try:
-                    x2, _, mo2, _ = next(ul_itr)
-                except StopIteration:
-                    ul_itr = iter(ul_loader); x2, _, mo2, _ = next(ul_itr)
+                x1, y_real, mo1, _ = next(lb)
+                x2, _, mo2, _ = next(ul)
                 x_real = torch.cat([x1.to(self.device, non_blocking=True), x2.to(self.device, non_blocking=True)], 0)
                 modal_org = torch.cat([mo1, mo2], 0)
                 scal = self.train_iteration(x_real, y_real.to(self.device, non_blocking=True), modal_org)
@@ -661,23 +650,8 @@ class UGANConsisTrainer(UGANShp0Trainer):
 
 
 def main(argv=None):
-    p = argparse.ArgumentParser()
-    p.add_argument("-p", "--phase", type=str, choices=("train", "test", "pseudo"))
-    p.add_argument("-f", "--fold", type=int, default=0)
-    p.add_argument("-nm", "--expr_name", type=str)
-    p.add_argument("-i", "--model_id", type=str, help="only for test")
-    p.add_argument("-wh", "--which_ckpt", type=str, default="last")
-    args = p.parse_args(argv)
-    seed_all()
-    trainer = UGANConsisTrainer(args.phase, args)
-    if args.phase == "train":
-        trainer.fit("inTurn")
-    elif args.phase == "test":
-        trainer.load_model(args.model_id, args.which_ckpt)
-        trainer.test("inTurn", pjoin(trainer.expr_root, args.model_id))
-    elif args.phase == "pseudo":
-        trainer.load_model(args.model_id, args.which_ckpt)
-        trainer.saving_pseudo("inTurn", pjoin(trainer.expr_root, args.model_id))
+    run_main(UGANConsisTrainer, make_parser(("train", "test", "pseudo"), model_id_help="only for test"), argv,
+             extra={"pseudo": "saving_pseudo"})
 
 
 if __name__ == "__main__":

@@ -1,16 +1,14 @@
 """``UGANTrainer`` (reference trainer/uganTrainer.py:33-229): the fully supervised predecessor of the consistency
 trainer -- ``UGAN`` (no PatchNCE head), every slice labeled, and a shape term DiceCE(seg(cycle), label) whose weight
 ramps with the epoch (:122-123) in place of the consistency / NCE terms.  D-step identical to the hot loop."""
-import argparse
 import random
 
-import numpy as np
 import torch
 
 from .. import config as cfg
 from .. import ops, parallel
 from ..network.ugan import UGAN, Discriminator
-from .baseTrainer import seed_all, make_adam, make_sgd
+from .baseTrainer import LoaderCycle, make_adam, make_parser, make_sgd, run_main
 from .uganShp0Trainer import UGANShp0Trainer
 
 SCALARS = ("D_real", "D_fake", "D_cls", "D_gp", "G_fake", "G_rec", "G_cls", "G_seg", "G_shp")
@@ -93,20 +91,15 @@ class UGANTrainer(UGANShp0Trainer):
         self.g_reducer.reduce()
         self.optimizer.step()
 
-        lr_ = self.poly_lr()
-        for grp in list(self.optimizer.param_groups) + list(self.d_optimizer.param_groups):
-            grp["lr"] = lr_
+        self.set_poly_lr(self.optimizer, self.d_optimizer)
         self.iter += 1
         return torch.stack([t.detach().float() for t in (d_real, d_fake, d_cls, d_gp, g_fake, g_rec, g_cls, g_seg, g_shp)])
 
     def train_epoch(self, lb_loader, ul_loader, meter):
         self.net.train(); self.D.train()
-        itr = iter(lb_loader)
+        batches = LoaderCycle(lb_loader)
         for i in range(self.n_critic * cfg.num_iter_per_epoch):
-            try:
-                x_real, y_real, modal_org, _ = next(itr)
-            except StopIteration:
-                itr = iter(lb_loader); x_real, y_real, modal_org, _ = next(itr)
+            x_real, y_real, modal_org, _ = next(batches)
             scal = self.train_iteration(x_real.to(self.device, non_blocking=True), y_real.to(self.device, non_blocking=True),
                                         modal_org)
             if meter is not None or (i + 1) % (self.n_critic * self.log_step) == 0:
@@ -120,20 +113,7 @@ class UGANTrainer(UGANShp0Trainer):
 
 
 def main(argv=None):
-    p = argparse.ArgumentParser()
-    p.add_argument("-p", "--phase", type=str, choices=("train", "test"))
-    p.add_argument("-f", "--fold", type=int, default=0)
-    p.add_argument("-nm", "--expr_name", type=str)
-    p.add_argument("-i", "--model_id", type=str)
-    p.add_argument("-wh", "--which_ckpt", type=str, default="last")
-    args = p.parse_args(argv)
-    seed_all()
-    t = UGANTrainer(args.phase, args)
-    if args.phase == "train":
-        t.fit("inTurn")
-    else:
-        t.load_model(args.model_id, args.which_ckpt)
-        t.test("inTurn", t.expr_root + "/" + args.model_id)
+    run_main(UGANTrainer, make_parser(("train", "test")), argv)
 
 
 if __name__ == "__main__":

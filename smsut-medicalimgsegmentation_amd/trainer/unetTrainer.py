@@ -1,16 +1,14 @@
 """``UnetTrainer`` (reference trainer/unetTrainer.py:35-85): supervised U-Net, SGD(0.9, wd 1e-3), poly LR --
 BASELINE configs 1-2."""
-import argparse
 import os
-import random
 
-import numpy as np
 import torch
 
 from .. import config as cfg
 from .. import graphs, ops, parallel
 from ..network.unet import UNet
-from .baseTrainer import seed_all, BaseTrainer, make_sgd, sgd_step
+from .baseTrainer import BaseTrainer, LoaderCycle, make_parser, make_sgd, run_main, sgd_step
+from .baseTrainer import seed_all  # noqa: F401  (callers that drive the trainer themselves seed through this module)
 
 
 class UnetTrainer(BaseTrainer):
@@ -75,15 +73,13 @@ class UnetTrainer(BaseTrainer):
             loss = self._bwd_phase(msk, stats)
         self.reducer.reduce()
         sgd_step(self.optimizer)
-        lr_ = self.poly_lr()
-        for g in self.optimizer.param_groups:
-            g["lr"] = lr_
+        self.set_poly_lr(self.optimizer)
         self.iter += 1
         return loss
 
     def train_epoch(self, lb_loader, ul_loader, meter):
         self.net.train()
-        it = iter(lb_loader)
+        batches = LoaderCycle(lb_loader)
         from ..misc.utils import ScalarFetcher
         fetch = ScalarFetcher(1, self.device)                # (the loss reaches the meter one iteration late: no device stall)
 
@@ -94,11 +90,7 @@ class UnetTrainer(BaseTrainer):
                 meter.accumulate(v, n)
         try:
             for _ in range(cfg.num_iter_per_epoch):
-                try:
-                    img, msk, mdl, _ = next(it)
-                except StopIteration:
-                    it = iter(lb_loader)
-                    img, msk, mdl, _ = next(it)
+                img, msk, mdl, _ = next(batches)
                 loss = self.train_step(img.to(self.device, non_blocking=True), msk.to(self.device, non_blocking=True))
                 consume(fetch.push(loss.reshape(1), (int(mdl[0]), img.size(0))))
         finally:
@@ -106,20 +98,7 @@ class UnetTrainer(BaseTrainer):
 
 
 def main(argv=None):
-    p = argparse.ArgumentParser()
-    p.add_argument("-p", "--phase", type=str, choices=("train", "test"))
-    p.add_argument("-f", "--fold", type=int, default=0)
-    p.add_argument("-nm", "--expr_name", type=str)
-    p.add_argument("-i", "--model_id", type=str)
-    p.add_argument("-wh", "--which_ckpt", type=str, default="last")
-    args = p.parse_args(argv)
-    seed_all()
-    t = UnetTrainer(args.phase, args)
-    if args.phase == "train":
-        t.fit("inTurn")
-    else:
-        t.load_model(args.model_id, args.which_ckpt)
-        t.test("inTurn", t.expr_root + "/" + args.model_id)
+    run_main(UnetTrainer, make_parser(("train", "test")), argv)
 
 
 if __name__ == "__main__":

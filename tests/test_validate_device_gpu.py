@@ -81,6 +81,26 @@ def test_unet_trainer_ragged_synthetic_loader(cfg_fix):
     assert_counts_are_the_volumes(prd, gt, counter, cfg.n_label + 1)
 
 
+@pytest.mark.parametrize("name", ("dtc", "meanTeacher", "crossPse"))
+def test_sibling_trainers_ragged_synthetic_loader(cfg_fix, name):
+    """The labelled / unlabelled siblings through the shared evaluation loop; dtc's ``_forward_eval`` hands it one element of the
+    network's tuple."""
+    import importlib
+    import dtc_ref
+    from smsut_amd.misc.synthetic import SyntheticSliceLoader
+    cfg = cfg_fix
+    cfg.input_size, cfg.batch_size = 64, 4
+    tr = getattr(importlib.import_module(f"smsut_amd.trainer.{name}Trainer"), f"{name}Trainer")("train", NS)
+    shapes = (dtc_ref.shapes if name == "dtc" else recipe.unet_shapes)(1, cfg.n_label + 1, cfg.base_width)
+    tr.net.load_state_dict(recipe.fill(shapes, 7))
+    test = SyntheticSliceLoader(3, size=64, n_batches=2, device="cuda")        # ragged: 3 < batch_size 4 -> padded
+    state = test.state_dict()
+    host, device, (prd, gt, counter) = both_paths(tr, cfg, test, rewind=lambda: test.load_state_dict(state))
+    assert host[0] == 6 and host[2].n["loss"] == 8                             # the PADDED batch size is what the meter counts
+    assert_same(host, device)
+    assert_counts_are_the_volumes(prd, gt, counter, cfg.n_label + 1)
+
+
 def test_ugan_trainer_on_the_recipe_validation_batches(cfg_fix, golden):
     from smsut_amd.trainer.uganConsisTrainer import UGANConsisTrainer
     g = golden("validate")
