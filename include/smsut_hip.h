@@ -627,13 +627,14 @@ int smsut_ema_chunk(void);
  *   empty and -1 where P is full.  One fp64 division and square root, rounded to fp32 once.
  * smsut_dtc_loss_fwd: t, z fp32 [N][HW][C], sdf [B][HW][C] pairing with the first B slices (1 <= B <= N), 1 <= C <= 16:
  *   out[2] = [mean over B C HW of (t - sdf)^2, mean over N C HW of (sigmoid(-k t) - softmax(z)_c)^2]; workgroup partials in double,
- *   summed in a fixed order (bitwise reproducible); finite for every t in [-1, 1] and any k.  workspace: smsut_dtc_ws(N, HW) floats.
+ *   summed in a fixed order (bitwise reproducible); finite for every t in [-1, 1] and any k.
+ *   workspace: the memory of smsut_dtc_ws(N, HW) floats, 8-byte aligned; the kernels keep doubles in it (hence void*).
  * smsut_dtc_loss_bwd: gt = gout[0] d out[0]/dt + gout[1] d out[1]/dt and gz = gout[1] d out[1]/dz in one launch (no gradient to sdf). */
 int64_t smsut_sdf_ws(int B, int C, int H, int W);
 int smsut_edt_sq(const int64_t* labels, int* d2, float* workspace, int* status, int B, int C, int H, int W, void* stream);
 int smsut_sdf_final(const int64_t* labels, const int* d2, const float* workspace, float* sdf, int B, int C, int H, int W, void* stream);
 int64_t smsut_dtc_ws(int N, int64_t HW);
-int smsut_dtc_loss_fwd(const float* t, const float* z, const float* sdf, float* out /*2*/, float* workspace, int N, int B, int64_t HW,
+int smsut_dtc_loss_fwd(const float* t, const float* z, const float* sdf, float* out /*2*/, void* workspace, int N, int B, int64_t HW,
                        int C, float k, void* stream);
 int smsut_dtc_loss_bwd(const float* t, const float* z, const float* sdf, const float* gout /*2*/, float* gt, float* gz, int N, int B,
                        int64_t HW, int C, float k, void* stream);

@@ -22,7 +22,6 @@
 //   time, and adds the total to out[i].
 // The grid is a function of P alone, so two calls on the same input give the same bits on any device.
 #include "common.h"
-#include "smsut_hip.h"
 
 namespace {
 constexpr int TPB = 256;

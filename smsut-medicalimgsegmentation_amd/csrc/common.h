@@ -4,6 +4,7 @@
 #include <stdint.h>
 #include <stdlib.h>
 #include <type_traits>
+#include "smsut_hip.h"      // the C ABI: every definition of an entry point is compiled against its declaration
 
 #define SMSUT_OK 0
 #define SMSUT_EINVAL (-1)

@@ -12,7 +12,6 @@
 // order; per-split slabs are summed by a second tiny kernel (deterministic, no atomics).
 #include "conv_mfma.h"
 #include "conv_wgrad_rr.h"
-#include "smsut_hip.h"       // smsut_conv2d_k4_supported, smsut_convT2x2_mfma_supported (conv_mfma.hip)
 
 namespace {
 

@@ -336,7 +336,7 @@ int smsut_sdf_final(const int64_t* labels, const int* d2, const float* workspace
 int64_t smsut_dtc_ws(int N, int64_t HW) { return 4 * (int64_t)N * dtc_blocks(HW); }
 
 // out[2] = [mean over B C HW of (t[:B] - sdf)^2, mean over N C HW of (sigmoid(-k t) - softmax(z)_c)^2]; t, z [N][HW][C], sdf [B][HW][C]
-int smsut_dtc_loss_fwd(const float* t, const float* z, const float* sdf, float* out, float* workspace, int N, int B, int64_t HW, int C,
+int smsut_dtc_loss_fwd(const float* t, const float* z, const float* sdf, float* out, void* workspace, int N, int B, int64_t HW, int C,
                        float k, void* stream) {
   SMSUT_REQUIRE(t && z && sdf && out && workspace && N > 0 && B >= 1 && B <= N && HW > 0 && C >= 1 && C <= MAXC);
   const int pb = dtc_blocks(HW);

@@ -14,7 +14,6 @@
 #include <algorithm>
 
 #include "common.h"
-#include "smsut_hip.h"
 
 namespace {
 

@@ -12,7 +12,6 @@
 // Integer adds only on the way to the table and IEEE fp32 steps in a fixed order inside it: the result is bit-reproducible and
 // is held to bit equality with Pillow (tests/golden/photometric_pil.npz).
 #include "common.h"
-#include "smsut_hip.h"
 
 namespace {
 

@@ -3,7 +3,6 @@
 // LDS by member rows.  The access pattern and the LDS image layout are described at the top of tta.hip.
 #pragma once
 #include "common.h"
-#include "smsut_hip.h"
 
 namespace {
 constexpr int TPB = 256;

@@ -8,7 +8,6 @@
 #include <cmath>
 
 #include "common.h"
-#include "smsut_hip.h"
 
 namespace {
 

@@ -1,5 +1,6 @@
 """CPU checks of the drop-in boundary: the C-ABI library loads here (no GPU), exports every symbol that
-include/smsut_hip.h declares, and the ctypes table in _hip.py agrees with the header argument-for-argument.
+include/smsut_hip.h declares and nothing else, every definition is compiled against that header, and the binding _hip.py reads
+from it agrees with this file's own reading argument-for-argument and refuses a tensor that does not fit its parameter.
 No compute entry point is called."""
 import ctypes
 import os
@@ -60,6 +61,104 @@ def test_ctypes_table_matches_header(built):
         assert got == decls[name][1], (name, got, decls[name][1])
         assert (decls[name][0] == "int64_t") == (name in _hip._RET_I64), name
     _hip.load()
+
+
+_SLABS = {"smsut_conv2d_wgrad_mfma_slabs", "smsut_conv2d_wgrad_pair_slabs"}     # take a stream, return a count of split slabs
+
+
+def test_status_follows_from_the_trailing_stream():
+    """An entry point returns a status exactly when its last parameter is ``void* stream`` (it enqueues work), but for the two
+    measurement entry points; read here from the header text, not through _hip's parser."""
+    import smsut_amd  # noqa: F401
+    from smsut_amd import _hip
+    txt = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
+    seen = 0
+    for m in re.finditer(r"\b(?:int|int64_t)\s+(smsut_\w+)\s*\(([^;]*?)\)\s*;", txt, flags=re.S):
+        name, streamed = m.group(1), re.search(r"(^|,)\s*void\s*\*\s*stream\s*$", m.group(2)) is not None
+        assert (name in _hip._NO_STATUS) == (not streamed or name in _SLABS), name
+        seen += 1
+    assert seen == len(header_decls()) and _hip._NO_STATUS <= set(header_decls())
+    assert _SLABS <= set(header_decls())
+
+
+def test_library_exports_nothing_undeclared(built):
+    """The other direction of test_library_exports_every_declared_symbol: every defined dynamic symbol with the C name smsut_* is
+    declared in the header (the internal C++ interfaces are mangled and do not match).  Read with the llvm-readelf that ships
+    with the compiler."""
+    import subprocess
+    llvm_bin = os.path.join(os.path.dirname(os.path.dirname(os.path.realpath(ge.HIPCC))), "lib", "llvm", "bin")
+    out = subprocess.check_output([os.path.join(llvm_bin, "llvm-readelf"), "--dyn-syms", "--wide", ge.LIB], text=True)
+    rows = [ln.split() for ln in out.splitlines()]
+    exported = {r[7].split("@")[0] for r in rows if len(r) == 8 and r[0].rstrip(":").isdigit() and r[6] != "UND"}
+    smsut = {n for n in exported if n.startswith("smsut_")}
+    decls = header_decls()
+    assert len(smsut) >= 50 and any(n.startswith("_Z") and "smsut_" in n for n in exported)       # the listing was read
+    assert smsut <= set(decls), sorted(smsut - set(decls))
+
+
+def test_every_definition_is_compiled_against_the_header():
+    """Each csrc/*.hip that defines entry points (an ``extern "C"``) includes include/smsut_hip.h, directly or through the project's
+    own headers, so a definition whose parameter list drifts from its declaration does not compile ("conflicting types")."""
+    def closure(path, seen):
+        for inc in re.findall(r'^\s*#\s*include\s+"([^"]+)"', open(path).read(), flags=re.M):
+            for d in (os.path.dirname(path), os.path.join(ge.ROOT, "include")):
+                f = os.path.join(d, inc)
+                if os.path.exists(f) and f not in seen:
+                    seen.add(f)
+                    closure(f, seen)
+        return seen
+    units = [os.path.join(ge.CSRC, f) for f in sorted(os.listdir(ge.CSRC)) if f.endswith(".hip")]
+    defining = [u for u in units if 'extern "C"' in open(u).read()]
+    assert len(defining) >= 18
+    for u in defining:
+        assert HEADER in closure(u, set()), f"{os.path.basename(u)} defines entry points without seeing smsut_hip.h"
+
+
+@pytest.fixture()
+def recorded(built, monkeypatch):
+    """``recorded(name)`` replaces the bound library function by a recorder and returns the list of argument tuples it was entered
+    with: nothing of the library runs."""
+    import smsut_amd  # noqa: F401
+    from smsut_amd import _hip
+    lib = _hip.load()
+
+    def install(name):
+        calls = []
+        getattr(lib, name)
+        monkeypatch.setattr(lib, name, lambda *a: calls.append(a) or 0)
+        return calls
+    return install
+
+
+def test_call_refuses_a_tensor_that_does_not_fit_its_parameter(recorded):
+    import torch
+    import smsut_amd  # noqa: F401
+    from smsut_amd import _hip
+    f32, f16, u8 = torch.zeros(8), torch.zeros(8, dtype=torch.float16), torch.zeros(8, dtype=torch.uint8)
+    add_act, expand, restail = recorded("smsut_add_act"), recorded("smsut_tta_expand"), recorded("smsut_restail_fwd_hs")
+    # int smsut_add_act(const float* a, const float* b /*nullable*/, float* y, int64_t n, float slope, void* stream)
+    with pytest.raises(_hip.SmsutHipError, match=r"smsut_add_act: argument 0 \(`const float\* a`\).*float32.*float16"):
+        _hip.call("smsut_add_act", f16, None, f32, 8, 0.1, 0)
+    with pytest.raises(_hip.SmsutHipError, match=r"smsut_add_act: argument 1 \(`const float\* b`\).*float32.*float16"):
+        _hip.call("smsut_add_act", None, f16, None, 8, 0.1, 0)
+    with pytest.raises(_hip.SmsutHipError, match=r"smsut_add_act: argument 3 \(`int64_t n`\).*number.*float32 tensor"):
+        _hip.call("smsut_add_act", None, None, None, f32, 0.1, 0)
+    with pytest.raises(_hip.SmsutHipError, match=r"smsut_add_act: argument 5 \(`void\* stream`\).*stream"):
+        _hip.call("smsut_add_act", None, None, None, 8, 0.1, f32)
+    # int smsut_tta_expand(const uint8_t* img, float* out, const int* transforms, int T, int N, int H, int W, void* stream)
+    with pytest.raises(_hip.SmsutHipError, match=r"smsut_tta_expand: argument 1 \(`float\* out`\).*float32.*uint8"):
+        _hip.call("smsut_tta_expand", None, u8, None, 1, 1, 2, 4, 0)
+    # a `void*` parameter takes any dtype: the fp16 tensor gets as far as the device check
+    with pytest.raises(_hip.SmsutHipError, match="need tensors on a HIP device"):
+        _hip.call("smsut_restail_fwd_hs", f16, *[None] * 10, 1, 2, 4, 0.1, 0)
+    with pytest.raises(_hip.SmsutHipError, match="need tensors on a HIP device"):
+        _hip.call("smsut_add_act", f32, None, f32, 8, 0.1, 0)                 # correctly typed, on the CPU
+    assert add_act == [] and expand == [] and restail == []                  # the library was never entered
+    # None (nullable) and plain ints (host addresses) pass in pointer slots, as they are
+    assert _hip.call("smsut_add_act", 4096, None, 8192, 8, 0.1, 0) == 0
+    assert add_act == [(4096, None, 8192, 8, 0.1, 0)]
+    with pytest.raises(TypeError):                                           # a wrong argument count stays ctypes' to report
+        _hip.call("smsut_in_chunks", 32, 65536)
 
 
 def test_support_queries_and_workspace_sizes(built):
