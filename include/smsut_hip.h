@@ -798,6 +798,29 @@ int smsut_tta_uncertain(const float* const* members, const int* transforms, uint
                         float* entropy /*nullable*/, float* mutual /*nullable*/, uint8_t* votes /*nullable*/,
                         int64_t* counts /*nullable*/, int T, int N, int H, int W, int C, int K, void* stream);
 
+/* ---------------------------------------------------------------------------------------------- sliding-window inference
+ * A slice larger than the window the network was trained on is predicted window by window, and the windows' class probabilities are
+ * blended on the slice's grid (csrc/window.hip; predict.py: Predictor.predict_windows).  The reference has no inference entry
+ * point: this replaces the zeros / strided multiply-add per window / division / argmax chain one would build from torch.
+ * smsut_window_blend: tiles[iy * nx + ix]: mean class probabilities fp32 [N][wh][ww][K] (the `prob` of smsut_tta_merge), 4-byte
+ *   aligned (a view that starts anywhere in its allocation), read in place; the tile covers rows ys[iy] .. ys[iy] + wh - 1 and
+ *   columns xs[ix] .. xs[ix] + ww - 1 of the grid [N][H][W].  `tiles` (ny * nx device pointers), `ys` (ny ints) and `xs` (nx ints)
+ *   are HOST arrays, read before the call returns; wy [wh] and wx [ww] are DEVICE tables of positive weights (the blend's
+ *   importance map is wy[i] * wx[j]).  Per output pixel (n, y, x), all in fp32, the tiles that cover it in row-major (iy, ix) order:
+ *     w_t = wy[y - ys[iy]] * wx[x - xs[ix]], rounded on its own;   s = w_0 + w_1 + ... in that order;   v_t = w_t / s (IEEE);
+ *     acc_k = v_0 p_0[k] + v_1 p_1[k] + ... in that order from 0.0f (the product of a term may be fused into its addition).
+ *   pred uint8 [N][H][W] = the first maximum of acc_k by smsut_argmax_channels' comparison (the first maximum wins, a NaN wins);
+ *   conf (nullable) fp32 [N][H][W] = acc_pred; prob (nullable) fp32 [N][H][W][K] = acc_k.  The weights are normalised before the
+ *   sum: under ONE tile v = w / w = 1.0f and the tile's probabilities pass through bit for bit.  A pixel under no tile gets
+ *   acc = 0 and pred 0 (the Python wrapper refuses a plan that leaves one).  No atomics, no cross-thread sums: bitwise reproducible.
+ * Limits (otherwise SMSUT_EINVAL and nothing is launched; N == 0 returns SMSUT_OK without a launch): 1 <= ny * nx <= 64,
+ *   1 <= K <= SMSUT_TTA_MAX_CLASSES, N <= SMSUT_TTA_MAX_SLICES, 1 <= wh <= H <= SMSUT_TTA_MAX_DIM, 1 <= ww <= W <= SMSUT_TTA_MAX_DIM,
+ *   every tile inside the grid: 0 <= ys[iy] <= H - wh, 0 <= xs[ix] <= W - ww. */
+#define SMSUT_WINDOW_MAX_TILES 64  /* 1 <= ny * nx <= 64 */
+int smsut_window_blend(const float* const* tiles, const int* ys, const int* xs, const float* wy, const float* wx, uint8_t* pred,
+                       float* conf /*nullable*/, float* prob /*nullable*/, int ny, int nx, int N, int H, int W, int wh, int ww, int K,
+                       void* stream);
+
 /* ---------------------------------------------------------------------------------------------- calibration
  * How far the predicted probabilities of a batch can be trusted (csrc/calibration.hip; misc/utils.py: CalibrationMeter,
  * fit_temperature): the reliability table, negative log-likelihood, Brier score and the derivatives of the NLL by the inverse

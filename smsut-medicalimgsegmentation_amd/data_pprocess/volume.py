@@ -96,13 +96,28 @@ def window_bounds(vol, modality):
     return torch.where(f >= 0.5, b - d * (1.0 - f), a + d * f).float()         # numpy's _lerp
 
 
-def prepare_volume(image, label, spacing, modality, new_spacing=NEW_SPACING, crop_size=CROP_SIZE, label_lut=None):
+FIELDS_OF_VIEW = ("crop", "full")
+
+
+def prepare_volume(image, label, spacing, modality, new_spacing=NEW_SPACING, crop_size=CROP_SIZE, label_lut=None,
+                   field_of_view="crop"):
     """Raw ``image`` (any real dtype) and ``label`` (uint8, or None) ``[D, H, W]`` with voxel ``spacing`` -> ``(image_u8, label_u8,
     plan)``: both ``[new_z, crop, crop]`` uint8 on the device (``label_u8`` None without a label), ``plan`` the ``ResamplePlan``
     (``plan.spacing`` is what ``test_spacing`` takes).  ``label_lut``: 256 uint8 entries applied to the raw label values while
-    they are resampled (CHAOS' grey ranges -> classes, BTCV's label list)."""
+    they are resampled (CHAOS' grey ranges -> classes, BTCV's label list).
+
+    ``field_of_view``: ``'crop'`` is the reference's training preprocessing, the central ``crop_size`` window.  ``'full'`` returns
+    the whole resampled grid ``plan.new_size`` and a plan with ``start = (0, 0, 0)`` and ``out_size = new_size``, with which
+    ``restore_labels`` forces no zeros.  The 8-bit window bounds are still those of the central ``crop_size`` window (the intensity
+    mapping the network was trained with), applied to the whole grid; the index map is a function of ``i + start``, so the central
+    window of the full image is the cropped output."""
+    if field_of_view not in FIELDS_OF_VIEW:
+        raise ValueError(f"prepare_volume: field_of_view must be one of {list(FIELDS_OF_VIEW)}, got {field_of_view!r}")
     img = _device_tensor("image", image, torch.float32)
     plan = resample_plan(tuple(img.shape), spacing, new_spacing, crop_size)
+    crop = plan
+    if field_of_view == "full":
+        plan = ResamplePlan(plan.new_size, plan.spacing, (0, 0, 0), plan.new_size)
     old = tuple(img.shape)
     vol = ops.resample_volume(ops.bspline_coefficients(img), plan.out_size, old, plan.new_size, plan.start)
     label_u8 = None
@@ -116,13 +131,16 @@ def prepare_volume(image, label, spacing, modality, new_spacing=NEW_SPACING, cro
                 label_lut = torch.from_numpy(np.asarray(label_lut, dtype=np.uint8).reshape(256))
             lut = label_lut.to(device=lab.device, dtype=torch.uint8)
         label_u8 = ops.resample_labels(lab, plan.out_size, old, plan.new_size, plan.start, lut=lut)
-    image_u8 = ops.window_u8(vol, window_bounds(vol, modality))
+    (_, sy, sx), (_, ch, cw) = crop.start, crop.out_size
+    central = vol if plan is crop else vol[:, sy:sy + ch, sx:sx + cw].contiguous()
+    image_u8 = ops.window_u8(vol, window_bounds(central, modality))
     return image_u8, label_u8, plan
 
 
 def restore_labels(pred_u8, plan, old_size):
     """A label volume on the processed grid (``plan.out_size``) back on the native grid ``old_size`` by the inverse map
-    ``x = (j * new) / old - start``: nearest neighbour, 0 outside the crop."""
+    ``x = (j * new) / old - start``: nearest neighbour, 0 outside the plan's window (the crop; with a
+    ``field_of_view='full'`` plan the whole resampled grid)."""
     old = _check_size("old_size", old_size)
     pred = _device_tensor("pred_u8", pred_u8, torch.uint8)
     if tuple(pred.shape) != tuple(plan.out_size):

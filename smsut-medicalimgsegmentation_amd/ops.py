@@ -16,6 +16,7 @@ from __future__ import annotations
 
 import contextlib
 import math
+import numbers
 import os as _os
 from typing import NamedTuple, Optional
 
@@ -2938,6 +2939,148 @@ def tta_merge(members, transforms, classes=None, want_conf=False, want_prob=Fals
     keep, addr = _tta_host_ints(tr)
     H.call("smsut_tta_merge", ctypes.addressof(ptrs), addr, pred, conf, prob, len(zs), n, h, w, c, k, _s())
     del keep, ptrs
+    return pred, conf, prob
+
+
+# ------------------------------------------------------------------------------------------- sliding windows (csrc/window.hip)
+WINDOW_MAX_TILES = 64                                          # smsut_window_blend: ny * nx <= 64 (include/smsut_hip.h)
+WINDOW_BLENDS = ("gaussian", "constant")
+
+
+def window_plan(size, window, overlap=0.5):
+    """The origins of the windows of length ``window`` along an axis of length ``size``, as a tuple of ints: ``target = max(1,
+    int(window * (1 - overlap)))`` is the largest step, ``n = ceil((size - window) / target) + 1`` windows, origin ``i`` at
+    ``(i * (size - window)) // (n - 1)`` (``(0,)`` for ``n == 1``).  The first origin is 0, the last ``size - window``, they increase
+    strictly and consecutive ones are at most ``target <= window`` apart: every index is covered.  Pure host code, integer
+    arithmetic; ``ValueError`` unless ``1 <= window <= size`` and ``0 <= overlap < 1``."""
+    for name, v in (("size", size), ("window", window)):
+        if isinstance(v, bool) or not isinstance(v, numbers.Integral):
+            raise TypeError(f"window_plan: {name} must be an integer, got {v!r}")
+    if isinstance(overlap, bool) or not isinstance(overlap, numbers.Real):
+        raise TypeError(f"window_plan: overlap must be a number, got {overlap!r}")
+    size, window = int(size), int(window)
+    if not 1 <= window <= size:
+        raise ValueError(f"window_plan: needs 1 <= window <= size, got window {window}, size {size}")
+    if not 0 <= overlap < 1:
+        raise ValueError(f"window_plan: needs 0 <= overlap < 1, got {overlap}")
+    target = max(1, int(window * (1 - overlap)))
+    span = size - window
+    n = (span + target - 1) // target + 1
+    return (0,) if n == 1 else tuple((i * span) // (n - 1) for i in range(n))
+
+
+def window_weights(n, blend="gaussian", device=None):
+    """One axis of the separable importance map of a window of length ``n``, fp32 ``[n]`` on ``device``.  ``'gaussian'``:
+    ``exp(-0.5 * ((i - (n - 1) / 2) / (n / 8))**2)``, sigma = n / 8 (the nnU-Net and MONAI default), computed in fp64 on the host
+    and rounded once; ``'constant'``: ones.  Every value is finite and positive (at n = 256 the smallest is 3.6e-4, the corner
+    product 1.3e-7: a normal fp32 number)."""
+    if isinstance(n, bool) or not isinstance(n, numbers.Integral):
+        raise TypeError(f"window_weights: n must be an integer, got {n!r}")
+    if not 1 <= n <= TTA_MAX_DIM:
+        raise ValueError(f"window_weights: n must lie in 1..{TTA_MAX_DIM}, got {n}")
+    if blend not in WINDOW_BLENDS:
+        raise ValueError(f"window_weights: unknown blend {blend!r}; expected one of {list(WINDOW_BLENDS)}")
+    n = int(n)
+    if blend == "constant":
+        w = [1.0] * n
+    else:
+        w = [math.exp(-0.5 * ((i - (n - 1) / 2) / (n / 8)) ** 2) for i in range(n)]
+    return torch.tensor(w, dtype=torch.float64).to(torch.float32).to(device)
+
+
+def _window_origins(what, name, origins, window, size):
+    """One axis of a plan: integers, strictly increasing, every window inside ``[0, size)`` and every index under one."""
+    try:
+        origins = list(origins)
+    except TypeError:
+        raise TypeError(f"{what}: {name} must be a sequence of integers, got {type(origins).__name__}") from None
+    for o in origins:
+        if isinstance(o, bool) or not isinstance(o, numbers.Integral):
+            raise TypeError(f"{what}: {name} must be integers, got {o!r}")
+    origins = [int(o) for o in origins]
+    if not origins:
+        raise ValueError(f"{what}: {name} is empty")
+    if any(b <= a for a, b in zip(origins, origins[1:])):
+        raise ValueError(f"{what}: {name} must increase strictly, got {origins}")
+    if origins[0] < 0 or origins[-1] + window > size:
+        raise ValueError(f"{what}: a window of {window} at {name} {origins} leaves the grid's axis of {size}")
+    if origins[0] > 0 or origins[-1] + window < size or any(b > a + window for a, b in zip(origins, origins[1:])):
+        raise ValueError(f"{what}: windows of {window} at {name} {origins} leave an index of the axis of {size} uncovered")
+    return origins
+
+
+def window_blend(tiles, ys, xs, grid_hw, wy, wx, want_conf=False, want_prob=False):
+    """Blend the windows of a sliding-window prediction in one pass (csrc/window.hip).  ``tiles``: ``len(ys) * len(xs)`` tensors in
+    row-major (iy, ix) order, each the mean class probabilities of one window as contiguous fp32 ``[N, wh, ww, K]`` (what
+    ``tta_merge(..., want_prob=True)`` returns; read in place, they are not stacked), window (iy, ix) lying at ``ys[iy], xs[ix]`` of
+    the grid ``grid_hw = (H, W)``; ``wy [wh]``, ``wx [ww]``: the two axes of the importance map on the device
+    (``window_weights``).  Per pixel the covering windows' weights ``wy * wx`` are normalised by their sum and the probabilities
+    averaged with them, in row-major window order, in fp32.  Returns ``(pred, conf, prob)``: ``pred`` uint8 ``[N, H, W]``, the
+    first maximum by ``argmax_channels``' rule; ``conf`` fp32 ``[N, H, W]``, the blended probability of that class, or None;
+    ``prob`` fp32 ``[N, H, W, K]`` or None.  Under one window a pixel's probabilities pass through bit for bit.  Bitwise
+    reproducible.  All checks run on the host before the device is touched: ``TypeError`` for what is no fp32 tensor or is on the CPU,
+    ``ValueError`` for a tile that is not contiguous ``[N, wh, ww, K]`` (it is not copied silently), a tile count other than
+    ``len(ys) * len(xs)`` or above 64, origins that do not increase strictly, leave the grid or leave an index uncovered, and
+    weight tables of another length or device."""
+    import ctypes
+    what = "window_blend"
+    try:
+        tiles = list(tiles)
+    except TypeError:
+        raise TypeError(f"{what}: tiles must be a sequence of tensors, got {type(tiles).__name__}") from None
+    for name, t in [(f"tile {i}", t) for i, t in enumerate(tiles)] + [("wy", wy), ("wx", wx)]:
+        if not isinstance(t, torch.Tensor):
+            raise TypeError(f"{what}: {name} must be a tensor, got {type(t).__name__}")
+        if t.dtype != torch.float32:
+            raise TypeError(f"{what}: {name} must be float32, got {t.dtype}")
+    if not tiles:
+        raise ValueError(f"{what}: needs at least one tile")
+    if tiles[0].dim() != 4:
+        raise ValueError(f"{what}: expected tiles [N, wh, ww, K], got shape {tuple(tiles[0].shape)}")
+    n, wh, ww, k = tiles[0].shape
+    try:
+        h, w = (int(v) for v in grid_hw)
+    except (TypeError, ValueError):
+        raise ValueError(f"{what}: grid_hw must be two integers (H, W), got {grid_hw!r}") from None
+    if not (1 <= wh <= h <= TTA_MAX_DIM and 1 <= ww <= w <= TTA_MAX_DIM):
+        raise ValueError(f"{what}: needs 1 <= window <= grid <= {TTA_MAX_DIM} on both axes, got window {(wh, ww)}, grid {(h, w)}")
+    ys = _window_origins(what, "ys", ys, wh, h)
+    xs = _window_origins(what, "xs", xs, ww, w)
+    if len(tiles) != len(ys) * len(xs):
+        raise ValueError(f"{what}: {len(tiles)} tiles for {len(ys)} x {len(xs)} origins")
+    if len(tiles) > WINDOW_MAX_TILES:
+        raise ValueError(f"{what}: at most {WINDOW_MAX_TILES} tiles, got {len(tiles)}")
+    if not 1 <= k <= TTA_MAX_CLASSES:
+        raise ValueError(f"{what}: classes must lie in 1..{TTA_MAX_CLASSES}, got {k}")
+    if n > TTA_MAX_SLICES:
+        raise ValueError(f"{what}: at most {TTA_MAX_SLICES} slices, got {n}")
+    for i, t in enumerate(tiles):
+        if tuple(t.shape) != (n, wh, ww, k):
+            raise ValueError(f"{what}: tile {i} has shape {tuple(t.shape)}, tile 0 {(n, wh, ww, k)}")
+        if not t.is_contiguous():
+            raise ValueError(f"{what}: tile {i} is not contiguous [N, wh, ww, K] (strides {t.stride()}); it is not copied silently")
+    for name, t, length in (("wy", wy, wh), ("wx", wx, ww)):
+        if tuple(t.shape) != (length,) or not t.is_contiguous():
+            raise ValueError(f"{what}: {name} must be a contiguous [{length}] table, got shape {tuple(t.shape)}")
+    for i, t in enumerate(tiles):
+        if not t.is_cuda or t.device != tiles[0].device:
+            raise TypeError(f"{what}: tile {i} must be on the first tile's HIP device, got {t.device} (no CPU fallback)")
+    dev = tiles[0].device
+    for name, t in (("wy", wy), ("wx", wx)):
+        if t.device != dev:
+            raise ValueError(f"{what}: the tiles are on {dev}, {name} on {t.device}")
+    pred = torch.empty(n, h, w, dtype=torch.uint8, device=dev)
+    conf = torch.empty(n, h, w, dtype=torch.float32, device=dev) if want_conf else None
+    prob = torch.empty(n, h, w, k, dtype=torch.float32, device=dev) if want_prob else None
+    if n == 0:
+        return pred, conf, prob
+    zs = [t.detach() for t in tiles]
+    ptrs = (ctypes.c_void_p * len(zs))(*[z.data_ptr() for z in zs])
+    keep_y, addr_y = _tta_host_ints(ys)
+    keep_x, addr_x = _tta_host_ints(xs)
+    H.call("smsut_window_blend", ctypes.addressof(ptrs), addr_y, addr_x, wy.detach(), wx.detach(), pred, conf, prob, len(ys), len(xs),
+           n, h, w, wh, ww, k, _s())
+    del keep_y, keep_x, ptrs                                   # (the entry point has copied the tables into the kernel arguments)
     return pred, conf, prob
 
 

@@ -6,7 +6,9 @@
 the network sees the flipped / rotated copies of every slice (``ops.tta_expand``), and the class probabilities of all copies and all
 networks are averaged on the un-transformed grid in one pass (``ops.tta_merge``, csrc/tta.hip).  ``predict_volume`` wraps it between
 ``prepare_volume`` (raw scanner array -> processed grid) and ``restore_labels`` (labels back on the scanner's grid), with the test
-phase's 3-D connected-component cleanup in between.  ``uncertainty=True`` / ``--uncertainty`` adds, from the same pass over the
+phase's 3-D connected-component cleanup in between.  ``field_of_view='full'`` / ``--field-of-view full`` labels the whole resampled
+grid instead of its central 256 x 256 window: the network runs over overlapping windows (``Predictor.predict_windows``) whose class
+probabilities are blended in one pass (``ops.window_blend``, csrc/window.hip).  ``uncertainty=True`` / ``--uncertainty`` adds, from the same pass over the
 member logits (``ops.tta_uncertainty``, csrc/uncertainty.hip), per-voxel entropy, mutual information and vote count and the label-free
 per-structure agreement scores (``misc.utils.structure_agreement``).  Everything stays on the device; reading DICOM / NIfTI is the caller's business
 (``.npy`` in and out).  The reference has no inference entry point: its only path through a trained network is the test phase, which
@@ -23,7 +25,7 @@ import torch
 
 from . import config as cfg
 from . import ops
-from .data_pprocess.volume import CROP_SIZE, NEW_SPACING, ResamplePlan, prepare_volume, restore_labels
+from .data_pprocess.volume import CROP_SIZE, FIELDS_OF_VIEW, NEW_SPACING, ResamplePlan, prepare_volume, restore_labels
 from .misc.utils import StructureAgreement, format_quality_csv, structure_agreement
 
 
@@ -137,6 +139,65 @@ class Predictor:
                         conf[start:start + count] = c
         return pred, conf
 
+    def predict_windows(self, image_u8, window, overlap=0.5, blend="gaussian", confidence=False):
+        """Sliding-window inference over slices larger than the networks' training size.  ``image_u8``: uint8 ``[D, H, W]`` on the
+        device with ``H, W >= window``; the networks see square ``window x window`` tiles at the origins of ``ops.window_plan(H |
+        W, window, overlap)`` (square, so every transform set keeps working), and the tiles' class probabilities are blended on the
+        ``H x W`` grid with the importance map ``blend`` (``ops.window_weights``: ``'gaussian'`` or ``'constant'``) in one pass
+        (``ops.window_blend``, csrc/window.hip).  Returns ``(pred, conf)`` as ``predict_slices``.
+
+        Slices are grouped, and the last group padded, as in ``predict_slices``.  Per group and per tile: ``tta_expand`` of the
+        tile's slices, the forwards, the temperature scales, ``tta_merge(want_prob=True)`` -- for one member too, whose mean over
+        T = 1 is its softmax -- then one ``window_blend`` per group.  Working memory is one group's tiles; nothing is read back.
+        With one tile (the grid is the window) ``pred`` and ``conf`` are bitwise those of ``predict_slices(confidence=True)``."""
+        if not isinstance(image_u8, torch.Tensor) or image_u8.dtype != torch.uint8:
+            raise TypeError("predict_windows: image_u8 must be a uint8 tensor")
+        if image_u8.dim() != 3 or image_u8.shape[0] < 1:
+            raise ValueError(f"predict_windows: expected [D >= 1, H, W] slices, got shape {tuple(image_u8.shape)}")
+        if isinstance(window, bool) or not isinstance(window, numbers.Integral):
+            raise TypeError(f"predict_windows: window must be an integer, got {window!r}")
+        d, h, w = image_u8.shape
+        win = int(window)
+        if not 1 <= win <= min(h, w):
+            raise ValueError(f"predict_windows: needs 1 <= window <= H, W, got window {win} on slices of {h} x {w}")
+        ys, xs = ops.window_plan(h, win, overlap), ops.window_plan(w, win, overlap)
+        if len(ys) * len(xs) > ops.WINDOW_MAX_TILES:
+            raise ValueError(f"predict_windows: {len(ys)} x {len(xs)} windows of {win} at overlap {overlap} on {h} x {w}, at most "
+                             f"{ops.WINDOW_MAX_TILES}")
+        if blend not in ops.WINDOW_BLENDS:
+            raise ValueError(f"predict_windows: unknown blend {blend!r}; expected one of {list(ops.WINDOW_BLENDS)}")
+        ops._tta_check_plane("predict_windows", (), h, w)                   # (the tiles are square: any transform fits them)
+        if not image_u8.is_cuda:
+            raise TypeError(f"predict_windows: image_u8 must be on a HIP device, got {image_u8.device} (no CPU fallback)")
+        image_u8 = image_u8.contiguous()
+        for f in self.forwards:
+            for m in _modules_of(f):
+                m.eval()
+        bs, tr, dev = self.batch_size, self.transforms, image_u8.device
+        weights = ops.window_weights(win, blend, dev)
+        pred = torch.empty(d, h, w, dtype=torch.uint8, device=dev)
+        conf = torch.empty(d, h, w, dtype=torch.float32, device=dev) if confidence else None
+        scale = [s for s in self.scales for _ in range(len(tr))]
+        with torch.no_grad():
+            for start, count, padding in self.plan(d):
+                tiles = []
+                for y0 in ys:
+                    for x0 in xs:
+                        x = ops.tta_expand(image_u8[start:start + count, y0:y0 + win, x0:x0 + win], tr)   # [T, count, 1, win, win]
+                        if padding:
+                            full = torch.zeros(len(tr), bs, 1, win, win, dtype=torch.float32, device=dev)
+                            full[:, :count] = x
+                            x = full
+                        outs = [f(x[t])[:count] for f in self.forwards for t in range(len(tr))]
+                        k = outs[0].shape[1] if self.classes is None else self.classes
+                        outs = [o if s is None else o * s for o, s in zip(outs, scale)]
+                        tiles.append(ops.tta_merge(outs, tr * len(self.forwards), classes=k, want_prob=True)[2])
+                p, c, _ = ops.window_blend(tiles, ys, xs, (h, w), weights, weights, want_conf=confidence)
+                pred[start:start + count] = p
+                if confidence:
+                    conf[start:start + count] = c
+        return pred, conf
+
     def predict_uncertain(self, image_u8):
         """``predict_slices(confidence=True)`` with the uncertainty of the prediction (``ops.tta_uncertainty``): returns
         ``UncertainSlices(pred, conf, entropy, mutual_info, votes, counts)``, the maps ``[D, H, W]`` on the device and ``counts``
@@ -191,7 +252,7 @@ class UncertainSlices(NamedTuple):
 
 class PredictResult(NamedTuple):
     labels: torch.Tensor                       # uint8: on the scanner's grid when restored, else the processed grid
-    labels_processed: torch.Tensor             # uint8 [new_z, crop, crop]: the processed grid, after the cleanup
+    labels_processed: torch.Tensor             # uint8 [new_z, crop, crop] (field_of_view='full': plan.new_size): the processed grid, after the cleanup
     confidence: Optional[torch.Tensor]         # fp32, processed grid, or None
     plan: ResamplePlan
 
@@ -209,7 +270,7 @@ class UncertainResult(NamedTuple):
 
 
 def predict_volume(predictor, image, spacing, modality, cleanup=True, restore=True, confidence=False, new_spacing=NEW_SPACING,
-                   crop_size=CROP_SIZE, uncertainty=False):
+                   crop_size=CROP_SIZE, uncertainty=False, field_of_view="crop", overlap=0.5, blend="gaussian"):
     """Raw ``image`` ``[D, H, W]`` (NumPy array or device tensor, any real dtype) with voxel ``spacing`` ``(sz, sy, sx)`` ->
     ``PredictResult``: ``prepare_volume`` -> ``predictor.predict_slices`` -> the test phase's 3-D 18-neighbour connected-component
     cleanup (``cleanup``) -> ``restore_labels`` onto the input's grid (``restore``).  The confidence stays on the processed grid.
@@ -217,9 +278,21 @@ def predict_volume(predictor, image, spacing, modality, cleanup=True, restore=Tr
     ``uncertainty``: the slices go through ``predictor.predict_uncertain`` instead and the result is an ``UncertainResult``: the
     same four fields (the same labels, bit for bit), the entropy, mutual-information and vote maps on the processed grid, and
     ``quality``, the label-free per-structure scores.  The maps, the counts and ``quality`` describe the prediction BEFORE the
-    connected-component cleanup: the members' agreement on what the networks said, not on what the cleanup kept."""
-    image_u8, _, plan = prepare_volume(image, None, spacing, modality, new_spacing=new_spacing, crop_size=crop_size)
-    if uncertainty:
+    connected-component cleanup: the members' agreement on what the networks said, not on what the cleanup kept.
+
+    ``field_of_view``: ``'crop'`` (the default) predicts the central ``crop_size`` window of the resampled grid, the training
+    preprocessing, and ``labels`` is 0 outside it.  ``'full'`` predicts the whole resampled grid by sliding windows of ``crop_size``
+    (``predictor.predict_windows`` with ``overlap`` and ``blend``): ``labels_processed`` and ``confidence`` are on the full grid,
+    ``plan`` is the full plan.  Not together with ``uncertainty`` (``ValueError``): the per-member maps across tiles are not built."""
+    if field_of_view not in FIELDS_OF_VIEW:
+        raise ValueError(f"predict_volume: field_of_view must be one of {list(FIELDS_OF_VIEW)}, got {field_of_view!r}")
+    if uncertainty and field_of_view == "full":
+        raise ValueError("predict_volume: uncertainty=True is not available with field_of_view='full'")
+    image_u8, _, plan = prepare_volume(image, None, spacing, modality, new_spacing=new_spacing, crop_size=crop_size,
+                                       field_of_view=field_of_view)
+    if field_of_view == "full":
+        pred, conf = predictor.predict_windows(image_u8, int(crop_size), overlap=overlap, blend=blend, confidence=confidence)
+    elif uncertainty:
         u = predictor.predict_uncertain(image_u8)
         pred, conf = u.pred, (u.conf if confidence else None)
     else:
@@ -254,6 +327,12 @@ def make_parser():
                    "grid) and quality.csv: label-free agreement scores per structure")
     p.add_argument("--temperature", default=None, help="temperature scaling of the probabilities: a number, or the path of the "
                    "temperature.txt that -p test writes with config.test_calibration")
+    p.add_argument("--field-of-view", dest="field_of_view", default="crop", choices=list(FIELDS_OF_VIEW),
+                   help="'crop' labels the central 256 x 256 window of the resampled grid (0 outside it); 'full' labels the whole "
+                   "grid by blended sliding windows")
+    p.add_argument("--overlap", type=float, default=0.5, help="--field-of-view full: the windows' overlap, 0 <= overlap < 1")
+    p.add_argument("--blend", default="gaussian", choices=list(ops.WINDOW_BLENDS), help="--field-of-view full: the windows' "
+                   "importance map")
     p.add_argument("--batch_size", type=int, default=None)
     p.add_argument("--out", required=True, help="directory for labels.npy, labels_processed.npy (and confidence.npy, and the files of "
                    "--uncertainty)")
@@ -303,7 +382,7 @@ def main(argv=None):
                           temperature=read_temperature(args.temperature))
     image = np.load(args.image)
     res = predict_volume(predictor, image, tuple(args.spacing), args.modality, confidence=args.confidence,
-                         uncertainty=args.uncertainty)
+                         uncertainty=args.uncertainty, field_of_view=args.field_of_view, overlap=args.overlap, blend=args.blend)
     os.makedirs(args.out, exist_ok=True)
     np.save(os.path.join(args.out, "labels.npy"), res.labels.cpu().numpy())
     np.save(os.path.join(args.out, "labels_processed.npy"), res.labels_processed.cpu().numpy())
